@@ -1,6 +1,6 @@
 """bench.py -- query-doc pairs/sec of the contrastive GradCache training step (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 runs in this process.  N > 1 without a torch.distributed environment re-launches ITSELF as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -14,8 +14,16 @@ cosine schedule.  A step = everything in the reference's training_step (sc/train
 embedding all-gather, fused loss fwd/bwd, pass 2 (re-forward + backward), gradient all-reduce, clip, AdamW, scheduler,
 bf16 shadow refresh.  Synthetic token ids are staged in HBM before the timed region.
 
-The JSON line carries, besides the contract fields:
+A plain run sets up, warms up, times the K steps of the metric and prints the line: the contract fields, `step_ms`,
+`config`, the schedule the step ran, and
   roofline      dominant kernel family (bf16 MFMA GEMMs) timed live with HIP events on its own stream (every 7th launch)
+
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32): `loss`, and a
+fixed, seeded sample (the same indices every run) of the fp32 master weights after the update (`params_sample`) and of
+the gradients the step left (`grads_sample`), with their flat indices (`sample_index`); the inputs are seeded, so two
+builds given the same arguments can be compared output for output.
+
+--full adds every secondary record below (each takes runs of its own beyond the K timed steps):
   weak          the same step at 2048 pairs per GPU (global batch 2048 x N: SURVEY.md §8(d) asks for both curves)
   resident      2048 pairs per GPU with pass 1's activations kept in HBM (no re-forward; identical results)
   dropin_chunk64  (N = 1) the same step at the reference recipe's GradCache chunk_size 64 (contrastive_pretrain.yaml:15)
@@ -78,7 +86,32 @@ def parse():
     # forward, 8 per layer backward) so that the sample walks through every shape; a stride of 8 always lands on the
     # same two (Wqkv forward, fc2-dgrad + SwiGLU backward) and over-reads the family average by ~4 %
     ap.add_argument("--prof-stride", type=int, default=7)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary record (box calibration, weak / resident / chunk-64 / auto-policy legs, "
+                         "exchange timings, the other BASELINE configs, the CPU baseline); off: only the headline metric")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the last timed step's loss and a seeded sample of the updated weights and gradients to DIR/*.npy")
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 21   # elements of the flat weight / gradient buffers sampled by --dump-outputs (32 MB in all)
+
+
+def dump_outputs(out_dir: str, torch, trunk, loss: float) -> None:
+    """What the last timed step hands its caller: the loss, and (sampled at fixed, seeded indices) the fp32 master weights
+    it updated and the gradients it left in the engine's flat buffers."""
+    import numpy as np
+
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    n = trunk.flat_param.numel()
+    g = torch.Generator().manual_seed(20240)
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=g).sort().values
+    idx_dev = idx.to(trunk.flat_param.device)
+    np.save(d / "loss.npy", np.array([loss], dtype=np.float32))
+    np.save(d / "params_sample.npy", trunk.flat_param.detach()[idx_dev].float().cpu().numpy())
+    np.save(d / "grads_sample.npy", trunk.flat_grad.detach()[idx_dev].float().cpu().numpy())
+    np.save(d / "sample_index.npy", idx.numpy().astype(np.float64))
 
 
 def usable_cores() -> int:
@@ -603,7 +636,7 @@ def main():
 
     # ---- what THIS box sustains, measured right before the metric: register-only bf16 MFMA loop + HBM copy
     box = {}
-    if not args.no_calibration:
+    if args.full and not args.no_calibration:
         try:
             from scripts.box_calibration import SmiSampler, calibrate
 
@@ -621,6 +654,8 @@ def main():
     dt, loss_last = run_leg(b, args.chunk_size, args.steps, args.warmup, prof=True, step_ms=step_ms)
     if sampler is not None:
         box.update(sampler.stop())
+    if args.dump_outputs and rank == 0:   # before any secondary leg trains the same tower further
+        dump_outputs(args.dump_outputs, torch, tower.trunk, loss_last)
     from contrastors_amd import loss as cx_loss
 
     sched_local = dict(cx_loss.LAST_SCHEDULE)
@@ -643,7 +678,7 @@ def main():
     peak_hbm = torch.cuda.max_memory_allocated(dev)
 
     extra = {}
-    if not args.no_extra_legs:
+    if args.full and not args.no_extra_legs:
         few = max(2, args.steps // 4)
         # weak-scaling curve: 2048 pairs per GPU whatever N is (coincides with the strong point at N = 8)
         if b != WEAK_PAIRS_PER_GPU and G >= WEAK_PAIRS_PER_GPU:
@@ -760,7 +795,7 @@ def main():
                            "train_args.exchange: auto)" + ("; under the shared-GPU test backend the numbers are not xGMI numbers"
                                                           if backend != "nccl" else ""))
             extra["xgmi_allgather"] = rec
-    if world == 1 and not args.no_extra_legs and not args.no_config_legs:
+    if world == 1 and args.full and not args.no_extra_legs and not args.no_config_legs:
         # the other BASELINE configs at their per-GPU shapes (the metric's tower is released first: they need the HBM)
         import gc
 
@@ -817,7 +852,8 @@ def main():
         out.update(flat_scalars(extra))
         out["whole_step_frac_of_mfma_peak"] = out["roofline"]["whole_step_frac_of_mfma_peak"]
         # per-box calibration (flat scalars: the driver's `parsed` view keeps scalars) + the nested record
-        out["box"] = box
+        if args.full:
+            out["box"] = box
         for k in ("mfma_probe_tflops", "blas_ref_tflops", "v6_same_shapes_tflops", "hbm_copy_tbs", "mean_sclk_mhz", "mean_power_w", "power_cap_w", "mfma_probe_clock_mhz", "mfma_probe_power_w"):
             if isinstance(box, dict) and isinstance(box.get(k), (int, float)):
                 out[f"box_{k}"] = box[k]
@@ -860,7 +896,7 @@ def main():
             out["weak_pairs_s_per_gpu"] = extra["weak"]["per_gpu"]
         elif world > 1 and b == WEAK_PAIRS_PER_GPU:
             out["weak_pairs_s_per_gpu"] = pairs_per_s / world
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess(S)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -268,6 +268,124 @@ def gen_hf_remap():
     print("hf_remap", {c: len(out[f"{c}/fwd_keys"]) for c in HF_REMAP_CASES})
 
 
+def _ref_file_module(name, path):
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location(name, str(path))
+    m = importlib.util.module_from_spec(spec)
+    sys.modules[name] = m
+    spec.loader.exec_module(m)
+    return m
+
+
+def _jsonable(v):
+    return json.loads(json.dumps(v, default=str))
+
+
+def gen_host_contracts():
+    """tests/golden/host_contracts.json + .npz: what the reference's own host-side code yields for the contracts
+    tests/test_host_cpu.py checks -- the training recipes of sc/configs/train as parsed YAML, sc/optimizer.py's decay
+    grouping of the engines' parameters, the reference's reading of a saved config.json, its hub-config conversions
+    (sc/models/encoder/bert.py, sc/models/vit/hf_vit.py, sc/models/vit/clip.py), the pooling selectors and LogitScale of
+    sc/models/biencoder/modeling_biencoder.py and the stream of sc/rand_state.py's RandContext."""
+    import dataclasses
+    import importlib
+    import tempfile
+    import types
+
+    import transformers
+    import yaml
+
+    from contrastors_amd import nomic_bert as nb
+    from contrastors_amd.biencoder import BiEncoderConfig, config_json
+    from contrastors_amd.vit import ViTConfig, ViTEngine
+
+    out, arrays = {}, {}
+    out["recipes"] = {p.name: yaml.safe_load(p.read_text()) for p in sorted((ref_import.REF_ROOT / "configs" / "train").glob("*.yaml"))}
+
+    ref_import.load()
+    ref_opt = importlib.import_module("contrastors.optimizer")
+    out["decay_groups"] = {}
+    for arch in ("nomic", "bert", "vit", "vit_clip"):
+        if arch in ("nomic", "bert"):
+            cfg = (nb.NomicBertConfig.nomic_bert_2048(vocab_size=128, n_layer=2) if arch == "nomic"
+                   else nb.NomicBertConfig.bert_base_uncased(vocab_size=128, n_layer=2))
+            cls = nb.NomicBertEngine
+        else:
+            cfg = ViTConfig(n_layer=2) if arch == "vit" else ViTConfig.clip_vit_base_patch16(n_layer=2)
+            cls = ViTEngine
+        fake = SimpleNamespace(config=cfg, _LAYER_PREFIX=cls._LAYER_PREFIX)
+        fake._layer_specs = lambda l, cls=cls, fake=fake: cls._layer_specs(fake, l)
+        decay, nodecay = cls._param_specs(fake)
+        mod = torch.nn.Module()
+        back = {}
+        for name, shape in decay + nodecay:
+            back[name.replace(".", "__")] = name
+            mod.register_parameter(name.replace(".", "__"), torch.nn.Parameter(torch.zeros(*shape)))
+        args = SimpleNamespace(weight_decay=0.01, learning_rate=1e-3, adam_beta1=0.9, adam_beta2=0.999, eps=1e-8)
+        opt = ref_opt.configure_optimizer([mod], args)
+        ids = {id(p): back[k] for k, p in mod.named_parameters()}
+        out["decay_groups"][arch] = {
+            "weight_decay": [g["weight_decay"] for g in opt.param_groups],
+            "decay": sorted(ids[id(p)] for p in opt.param_groups[0]["params"]),
+            "nodecay": sorted(ids[id(p)] for p in opt.param_groups[1]["params"])}
+
+    ref_bi = _ref_file_module("ref_bi_cfg", ref_import.REF_ROOT / "models" / "biencoder" / "configuration_biencoder.py")
+    ours = BiEncoderConfig(model_name="nomic-ai/nomic-bert-2048", pooling="mean", logit_scale=50.0, hamming=True,
+                           gradient_checkpointing=True, projection_dim=256, nomic_encoder=True, trainable_logit_scale=True)
+    saved = config_json(ours, nb.NomicBertConfig.nomic_bert_2048())
+    with tempfile.TemporaryDirectory() as tmp:
+        Path(tmp, "config.json").write_text(json.dumps(saved))
+        got = ref_bi.BiEncoderConfig.from_pretrained(tmp)
+    keys = ("model_name", "pooling", "logit_scale", "hamming", "gradient_checkpointing", "projection_dim", "nomic_encoder",
+            "trainable_logit_scale", "freeze", "pretrained", "use_fused_kernels", "trunk_config", "trunk_type")
+    out["biencoder_config"] = {"saved": _jsonable(saved), "loaded": _jsonable({k: getattr(got, k) for k in keys})}
+
+    enc = ref_import.REF_ROOT / "models" / "encoder"
+    pkg = types.ModuleType("ref_enc_pkg")
+    pkg.__path__ = [str(enc)]
+    sys.modules["ref_enc_pkg"] = pkg
+    for n in ("configuration_nomic_bert", "bert"):
+        mod = _ref_file_module(f"ref_enc_pkg.{n}", enc / f"{n}.py")
+    ref = mod.bert_config_to_nomic_config(transformers.BertConfig())
+    out["bert_base_conversion"] = _jsonable({f.name: getattr(ref, f.name) for f in dataclasses.fields(nb.NomicBertConfig)
+                                             if hasattr(ref, f.name)})
+    vit_dir = ref_import.REF_ROOT / "models" / "vit"
+    for key, ref in (("vit_base_patch16_224", _ref_file_module("ref_vit_hf_vit", vit_dir / "hf_vit.py")
+                      .hf_vit_config_to_vit_config(transformers.ViTConfig())),
+                     ("clip_vit_base_patch16", _ref_file_module("ref_vit_clip", vit_dir / "clip.py")
+                      .clip_config_to_vit_config(transformers.CLIPConfig(vision_config={"patch_size": 16})))):
+        out[f"vit_conversion/{key}"] = _jsonable({f.name: getattr(ref, f.name) for f in dataclasses.fields(ViTConfig)
+                                                  if hasattr(ref, f.name)})
+
+    bi = ref_import.load_biencoder()
+    g = torch.Generator().manual_seed(3)
+    h = torch.randn(5, 9, 32, generator=g)
+    lens = torch.tensor([9, 1, 4, 7, 2])
+    mask = (torch.arange(9)[None] < lens[:, None]).long()
+    ids = torch.zeros(5, 9, dtype=torch.long)
+    arrays.update({"pool/h": h.numpy(), "pool/mask": mask.numpy(), "pool/cls": bi.ClsSelector()(h, ids, mask).numpy(),
+                   "pool/mean": bi.MeanPooling()(h, ids, mask).numpy(), "pool/mean_nomask": bi.MeanPooling()(h, ids, None).numpy()})
+    ls = bi.LogitScale(SimpleNamespace(logit_scale=20.0, trainable_logit_scale=True))
+    arrays["logit_scale/out"] = ls(torch.ones(1)).detach().numpy()
+    out["logit_scale_trainable"] = bool(ls.logit_scale.requires_grad)
+
+    ref_rs = _ref_file_module("ref_rand_state", ref_import.REF_ROOT / "rand_state.py")
+    torch.manual_seed(11)
+    chunk = {"input_ids": torch.zeros(2, 3, dtype=torch.long)}
+    torch.rand(3)
+    ctx = ref_rs.RandContext(chunk)
+    arrays["rand/first"] = torch.rand(4).numpy()
+    arrays["rand/between"] = torch.rand(2).numpy()
+    with ctx:
+        arrays["rand/replay"] = torch.rand(4).numpy()
+    arrays["rand/after"] = torch.rand(2).numpy()
+
+    (GOLD / "host_contracts.json").write_text(json.dumps(out, indent=1, sort_keys=True) + "\n")
+    np.savez_compressed(GOLD / "host_contracts.npz", **arrays)
+    print("host_contracts", sorted(out), sorted(arrays))
+
+
 def make_mlm_inputs(cfgd, B, S, seed, p=0.3):
     ids, mask, lens = make_inputs(cfgd, B, S, seed)
     g = torch.Generator().manual_seed(seed + 7)
@@ -594,6 +712,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "hf_remap":
         gen_hf_remap()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "host_contracts":
+        gen_host_contracts()
+        sys.exit(0)
     gen_encoder("encoder_nomic_tiny", TINY_NOMIC, 1)
     gen_encoder("encoder_bert_tiny", TINY_BERT, 2)
     # Dynamic-NTK rotary (modeling_hf_nomic_bert.py:1215-1235): sequences (32) longer than max_trained_positions (16)
@@ -610,3 +731,4 @@ if __name__ == "__main__":
     gen_mlm("mlm_bert_tiny", TINY_BERT, 22)
     gen_loader()
     gen_local_loader()
+    gen_host_contracts()

@@ -227,7 +227,7 @@ def test_bench_two_ranks_prints_one_json_line():
     port = 29800 + (os.getpid() % 90)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup",
-           "1", "--global-batch", "64", "--chunk-size", "16", "--layers", "2", "--no-cpu-baseline"]
+           "1", "--global-batch", "64", "--chunk-size", "16", "--layers", "2", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

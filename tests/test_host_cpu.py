@@ -12,12 +12,28 @@ from contrastors_amd.loss import make_labels
 from contrastors_amd.nomic_bert import VarlenBatch
 from contrastors_amd.trainers import _lr_lambda, synthetic_batches
 
-REF_YAML = Path("/root/reference/src/contrastors/configs/train/contrastive_pretrain.yaml")
+# what the reference's own host-side code yields (its recipes, optimizer grouping, config classes, hub-config conversions,
+# pooling selectors, RandContext): recorded by oracle/make_golden.py::gen_host_contracts
+CONTRACTS = Path(__file__).resolve().parent / "golden" / "host_contracts.json"
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
-def test_reference_recipe_yaml_loads_unchanged():
-    cfg = read_config(str(REF_YAML))
+def _contracts():
+    import json
+
+    return json.loads(CONTRACTS.read_text())
+
+
+def _recipe_path(name, tmp_path):
+    """The reference recipe sc/configs/train/<name> written back as a YAML file (its parsed mapping is stored)."""
+    import yaml
+
+    p = tmp_path / name
+    p.write_text(yaml.safe_dump(_contracts()["recipes"][name], sort_keys=False))
+    return p
+
+
+def test_reference_recipe_yaml_loads_unchanged(tmp_path):
+    cfg = read_config(str(_recipe_path("contrastive_pretrain.yaml", tmp_path)))
     assert cfg.train_args.grad_cache is True and cfg.train_args.chunk_size == 64
     assert cfg.train_args.learning_rate == 2e-4 and cfg.train_args.schedule_type == "cosine"
     assert cfg.model_args.logit_scale == 50 and cfg.model_args.pooling == "mean"
@@ -86,10 +102,9 @@ def test_synthetic_batches_follow_loader_contract():
     assert (b["query_input_ids"][b["query_attention_mask"] == 0] == 0).all()  # right padding with pad id 0
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
-def test_reference_mlm_recipe_yaml_loads_unchanged():
+def test_reference_mlm_recipe_yaml_loads_unchanged(tmp_path):
     """configs/train/mlm.yaml: the architecture overrides the MLM trainer reads (sc/trainers/mlm.py:20-40) survive."""
-    cfg = read_config(str(REF_YAML.parent / "mlm.yaml"))
+    cfg = read_config(str(_recipe_path("mlm.yaml", tmp_path)))
     ma, ta = cfg.model_args, cfg.train_args
     assert ma.model_type == "mlm" and ma.seq_len == 2048 and ma.rotary_emb_base == 500000
     assert ma.activation_function == "swiglu" and ma.rotary_emb_fraction == 1.0 and ma.pad_vocab_to_multiple_of == 64
@@ -319,23 +334,17 @@ def test_compact_swiglu_backward_identity():
     assert float(rel.max()) <= 2.0 ** -8 and float(rel.mean()) < 2.0 ** -9
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
 @pytest.mark.parametrize("arch", ["nomic", "bert", "vit", "vit_clip"])
 def test_decay_grouping_equals_the_reference_configure_optimizer(arch):
     """The engines lay their parameters out as [decay | no-decay] flat buffers (fused AdamW).  Which parameter
     goes where is the reference's rule (sc/optimizer.py:7-47: squeeze().ndim < 2, 'bias' in the name, logit_scale -> no
-    decay): run the reference's OWN configure_optimizer on a module carrying the engine's parameter names and shapes and
-    compare the two groups."""
+    decay): the groups the reference's OWN configure_optimizer made of a module carrying the engine's parameter names and
+    shapes (recorded in host_contracts.json) against the engine's two groups."""
     from types import SimpleNamespace
 
     from contrastors_amd import nomic_bert as nb
     from contrastors_amd.vit import ViTConfig, ViTEngine
-    from oracle import ref_import
 
-    ref_import.load()
-    import importlib
-
-    ref_opt = importlib.import_module("contrastors.optimizer")
     if arch in ("nomic", "bert"):
         cfg = (nb.NomicBertConfig.nomic_bert_2048(vocab_size=128, n_layer=2) if arch == "nomic"
                else nb.NomicBertConfig.bert_base_uncased(vocab_size=128, n_layer=2))
@@ -346,18 +355,9 @@ def test_decay_grouping_equals_the_reference_configure_optimizer(arch):
     fake = SimpleNamespace(config=cfg, _LAYER_PREFIX=cls._LAYER_PREFIX)
     fake._layer_specs = lambda l: cls._layer_specs(fake, l)
     decay, nodecay = cls._param_specs(fake)
-    mod = torch.nn.Module()
-    back = {}
-    for name, shape in decay + nodecay:
-        key = name.replace(".", "__")
-        back[key] = name
-        mod.register_parameter(key, torch.nn.Parameter(torch.zeros(*shape)))
-    args = SimpleNamespace(weight_decay=0.01, learning_rate=1e-3, adam_beta1=0.9, adam_beta2=0.999, eps=1e-8)
-    opt = ref_opt.configure_optimizer([mod], args)
-    ids = {id(p): back[k] for k, p in mod.named_parameters()}
-    ref_decay = {ids[id(p)] for p in opt.param_groups[0]["params"]}
-    ref_nodecay = {ids[id(p)] for p in opt.param_groups[1]["params"]}
-    assert opt.param_groups[0]["weight_decay"] == 0.01 and opt.param_groups[1]["weight_decay"] == 0.0
+    ref = _contracts()["decay_groups"][arch]
+    ref_decay, ref_nodecay = set(ref["decay"]), set(ref["nodecay"])
+    assert ref["weight_decay"] == [0.01, 0.0]
     assert ref_decay == {n for n, _ in decay}, ref_decay ^ {n for n, _ in decay}
     assert ref_nodecay == {n for n, _ in nodecay}, ref_nodecay ^ {n for n, _ in nodecay}
 
@@ -398,25 +398,24 @@ def test_reference_schema_keys_are_served_or_refused_never_dropped():
             ModelArgs(**bad)
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
-def test_every_reference_recipe_parses_or_is_refused_for_a_stated_reason():
+def test_every_reference_recipe_parses_or_is_refused_for_a_stated_reason(tmp_path):
     """All 17 recipes of sc/configs/train: the ones on the path parse unchanged; mixture-of-experts recipes are refused when the
     YAML is read (they used to parse with `num_experts` silently dropped, i.e. would have trained a dense model)."""
-    import glob
-
     ok, refused = [], {}
-    for f in sorted(glob.glob(str(REF_YAML.parent / "*.yaml"))):
+    names = sorted(_contracts()["recipes"])
+    assert len(names) == 17
+    for name in names:
         try:
-            read_config(f)
-            ok.append(Path(f).name)
+            read_config(str(_recipe_path(name, tmp_path)))
+            ok.append(name)
         except ValueError as e:
-            refused[Path(f).name] = str(e)
+            refused[name] = str(e)
     assert set(refused) == {"contrastive_finetune_moe.yaml", "contrastive_pretrain_multilingual.yaml",
                             "contrastive_pretrain_multilingual_full.yaml", "contrastive_pretrain_tk2.yaml"}, refused
     assert all("num_experts" in v for v in refused.values())
     assert {"contrastive_pretrain.yaml", "contrastive_matryoshka.yaml", "mlm.yaml", "mmlm.yaml", "nomic_embed_vision_v1.5.yaml",
             "contrastive_finetune.yaml"} <= set(ok) and len(ok) == 13
-    vis = read_config(str(REF_YAML.parent / "nomic_embed_vision_v1.5.yaml"))
+    vis = read_config(str(_recipe_path("nomic_embed_vision_v1.5.yaml", tmp_path)))
     assert vis.vision_model_args.logit_scale == pytest.approx(1 / 0.07)   # `logit_scale: null` -> the default (sc/config.py:193-196)
 
 
@@ -472,41 +471,35 @@ def test_train_cli_overrides():
         split_overrides(["stray"])
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
-def test_oracle_pooling_head_equals_the_reference_modules():
-    """oracle.encoder_ref.pool / the hamming LayerNorm / normalisation of `biencoder_embedding` against the reference's OWN
-    modules (sc/models/biencoder/modeling_biencoder.py:44-49 ClsSelector, :79-90 MeanPooling incl. its mask-free ViT branch,
-    :283 nn.LayerNorm(elementwise_affine=False), :317 F.normalize), imported by oracle/ref_import.load_biencoder()."""
-    from oracle import encoder_ref, ref_import
+def test_oracle_pooling_head_equals_the_reference_modules(gold):
+    """oracle.encoder_ref.pool / the hamming LayerNorm / normalisation of `biencoder_embedding` against what the reference's
+    OWN modules returned (sc/models/biencoder/modeling_biencoder.py:44-49 ClsSelector, :79-90 MeanPooling incl. its mask-free
+    ViT branch, :30-38 LogitScale; recorded in host_contracts.npz), and :283 nn.LayerNorm(elementwise_affine=False)."""
+    from oracle import encoder_ref
 
-    bi = ref_import.load_biencoder()
+    ref = gold("host_contracts")
     g = torch.Generator().manual_seed(3)
     h = torch.randn(5, 9, 32, generator=g)
     lens = torch.tensor([9, 1, 4, 7, 2])
     mask = (torch.arange(9)[None] < lens[:, None]).long()
-    ids = torch.zeros(5, 9, dtype=torch.long)
-    assert torch.equal(encoder_ref.pool(h, mask, "cls"), bi.ClsSelector()(h, ids, mask))
-    torch.testing.assert_close(encoder_ref.pool(h, mask, "mean"), bi.MeanPooling()(h, ids, mask), rtol=0, atol=0)
-    torch.testing.assert_close(encoder_ref.pool(h, None, "mean"), bi.MeanPooling()(h, ids, None), rtol=0, atol=0)
+    assert torch.equal(h, torch.from_numpy(ref["pool/h"])) and torch.equal(mask, torch.from_numpy(ref["pool/mask"]))
+    assert torch.equal(encoder_ref.pool(h, mask, "cls"), torch.from_numpy(ref["pool/cls"]))
+    torch.testing.assert_close(encoder_ref.pool(h, mask, "mean"), torch.from_numpy(ref["pool/mean"]), rtol=0, atol=0)
+    torch.testing.assert_close(encoder_ref.pool(h, None, "mean"), torch.from_numpy(ref["pool/mean_nomask"]), rtol=0, atol=0)
     e = encoder_ref.pool(h, mask, "mean")
     ham = torch.nn.LayerNorm(32, elementwise_affine=False)
     torch.testing.assert_close(torch.nn.functional.layer_norm(e, (32,)), ham(e), rtol=0, atol=0)
-    ls = bi.LogitScale(SimpleNamespace(logit_scale=20.0, trainable_logit_scale=True))
-    assert float(ls(torch.ones(1)).detach()) == pytest.approx(20.0, rel=1e-6) and ls.logit_scale.requires_grad
+    assert float(ref["logit_scale/out"][0]) == pytest.approx(20.0, rel=1e-6) and _contracts()["logit_scale_trainable"]
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
-def test_rand_context_behaves_like_the_reference_class_on_the_cpu_generator():
-    """rand_state.RandContext against sc/rand_state.py:6-22 (the reference's own class, loaded from its file): numbers drawn
-    inside `with ctx:` replay the stream that followed the snapshot, and the outer stream continues afterwards as if the
-    block had not run; `needed=False` (dropout 0: the saving this port makes) leaves the generator alone entirely."""
-    import importlib.util
-
+def test_rand_context_behaves_like_the_reference_class_on_the_cpu_generator(gold):
+    """rand_state.RandContext against sc/rand_state.py:6-22 (the reference's own class; the stream it produced under the
+    same schedule is recorded in host_contracts.npz): numbers drawn inside `with ctx:` replay the stream that followed the
+    snapshot, and the outer stream continues afterwards as if the block had not run; `needed=False` (dropout 0: the saving
+    this port makes) leaves the generator alone entirely."""
     from contrastors_amd.rand_state import RandContext
 
-    spec = importlib.util.spec_from_file_location("ref_rand_state", str(REF_YAML.parents[2] / "rand_state.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    ref = gold("host_contracts")
 
     def run(cls, **kw):
         torch.manual_seed(11)
@@ -520,7 +513,7 @@ def test_rand_context_behaves_like_the_reference_class_on_the_cpu_generator():
         after = torch.rand(2)
         return first, between, replay, after
 
-    a, b = run(ref.RandContext), run(RandContext)
+    a, b = tuple(torch.from_numpy(ref[f"rand/{k}"]) for k in ("first", "between", "replay", "after")), run(RandContext)
     for x, y in zip(a, b):
         assert torch.equal(x, y)
     assert torch.equal(b[0], b[2])          # the replay IS pass 1's stream
@@ -528,59 +521,42 @@ def test_rand_context_behaves_like_the_reference_class_on_the_cpu_generator():
     assert torch.equal(off[0], a[0]) and not torch.equal(off[2], off[0])   # no snapshot, no replay: the stream just continues
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
-def test_saved_config_json_loads_with_the_reference_biencoder_config(tmp_path):
+def test_saved_config_json_loads_with_the_reference_biencoder_config():
     """BiEncoder.save_pretrained's config.json through the reference's own BiEncoderConfig.from_pretrained
-    (sc/models/biencoder/configuration_biencoder.py:4-31; what sc/trainers/text_text.py:148-159 does with `checkpoint:`)."""
-    import importlib.util
+    (sc/models/biencoder/configuration_biencoder.py:4-31; what sc/trainers/text_text.py:148-159 does with `checkpoint:`):
+    the file written today is the one the reference read (host_contracts.json), and what it read equals our config."""
     import json
 
     from contrastors_amd.biencoder import BiEncoderConfig, config_json
     from contrastors_amd.nomic_bert import NomicBertConfig
 
-    spec = importlib.util.spec_from_file_location(
-        "ref_bi_cfg", str(REF_YAML.parents[2] / "models" / "biencoder" / "configuration_biencoder.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    ref = _contracts()["biencoder_config"]
     ours = BiEncoderConfig(model_name="nomic-ai/nomic-bert-2048", pooling="mean", logit_scale=50.0, hamming=True,
                            gradient_checkpointing=True, projection_dim=256, nomic_encoder=True, trainable_logit_scale=True)
-    (tmp_path / "config.json").write_text(json.dumps(config_json(ours, NomicBertConfig.nomic_bert_2048())))
-    got = ref.BiEncoderConfig.from_pretrained(str(tmp_path))
+    assert json.loads(json.dumps(config_json(ours, NomicBertConfig.nomic_bert_2048()))) == ref["saved"]
+    got = SimpleNamespace(**ref["loaded"])
     for k in ("model_name", "pooling", "logit_scale", "hamming", "gradient_checkpointing", "projection_dim", "nomic_encoder",
               "trainable_logit_scale", "freeze", "pretrained", "use_fused_kernels"):
         assert getattr(got, k) == getattr(ours, k), k
     assert got.trunk_config["n_layer"] == 12 and got.trunk_type == "NomicBertConfig"
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
 def test_bert_base_architecture_equals_the_reference_conversion_of_the_hf_config():
     """NomicBertConfig.bert_base_uncased(hf_dropout=True) against sc/models/encoder/bert.py:11-50 bert_config_to_nomic_config
     applied to transformers.BertConfig() (= bert-base-uncased's hub config): every field the engine reads, the dropout
-    probabilities 0.1 the conversion carries over included; without the flag only those three differ."""
+    probabilities 0.1 the conversion carries over included; without the flag only those three differ.  The converted
+    configuration is recorded in host_contracts.json."""
     import dataclasses
-    import importlib.util
-    import sys
-    import types
+    import json
 
-    transformers = pytest.importorskip("transformers")
     from contrastors_amd.biencoder import _default_trunk_config
     from contrastors_amd.nomic_bert import NomicBertConfig
 
-    enc = REF_YAML.parents[2] / "models" / "encoder"
-    pkg = types.ModuleType("ref_enc_pkg")
-    pkg.__path__ = [str(enc)]
-    sys.modules["ref_enc_pkg"] = pkg
-    mods = {}
-    for n in ("configuration_nomic_bert", "bert"):
-        spec = importlib.util.spec_from_file_location(f"ref_enc_pkg.{n}", str(enc / f"{n}.py"))
-        mods[n] = importlib.util.module_from_spec(spec)
-        sys.modules[f"ref_enc_pkg.{n}"] = mods[n]
-        spec.loader.exec_module(mods[n])
-    ref = mods["bert"].bert_config_to_nomic_config(transformers.BertConfig())
+    ref = _contracts()["bert_base_conversion"]
     ours = NomicBertConfig.bert_base_uncased(hf_dropout=True)
     skip = {"rotary_emb_base", "max_position_embeddings", "rotary_scaling_factor", "max_trained_positions"}  # (no rotary in BERT)
-    diff = {f.name for f in dataclasses.fields(ours) if f.name not in skip and hasattr(ref, f.name)
-            and getattr(ref, f.name) != getattr(ours, f.name)}
+    diff = {f.name for f in dataclasses.fields(ours) if f.name not in skip and f.name in ref
+            and ref[f.name] != json.loads(json.dumps(getattr(ours, f.name), default=str))}
     assert diff == set(), diff
     assert (ours.resid_pdrop, ours.embd_pdrop, ours.attn_pdrop) == (0.1, 0.1, 0.1)
     plain = NomicBertConfig.bert_base_uncased()
@@ -589,28 +565,21 @@ def test_bert_base_architecture_equals_the_reference_conversion_of_the_hf_config
     assert _default_trunk_config("bert-base-uncased") == ours
 
 
-@pytest.mark.skipif(not REF_YAML.exists(), reason="reference tree only exists in the build container")
 def test_vit_architectures_equal_the_reference_conversions_of_the_hf_configs():
     """ViTConfig.vit_base_patch16_224() against sc/models/vit/hf_vit.py:9-53 applied to transformers.ViTConfig()
     (google/vit-base-patch16-224) and ViTConfig.clip_vit_base_patch16() against sc/models/vit/clip.py:9-55 applied to the
-    vision half of transformers.CLIPConfig with patch 16 (openai/clip-vit-base-patch16): every field of ours, equal."""
+    vision half of transformers.CLIPConfig with patch 16 (openai/clip-vit-base-patch16): every field of ours, equal.  The
+    converted configurations are recorded in host_contracts.json."""
     import dataclasses
-    import importlib.util
+    import json
 
-    transformers = pytest.importorskip("transformers")
     from contrastors_amd.vit import ViTConfig
 
-    def load(name):
-        spec = importlib.util.spec_from_file_location(f"ref_vit_{name}", str(REF_YAML.parents[2] / "models" / "vit" / f"{name}.py"))
-        m = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(m)
-        return m
-
-    for ours, ref in ((ViTConfig.vit_base_patch16_224(), load("hf_vit").hf_vit_config_to_vit_config(transformers.ViTConfig())),
-                      (ViTConfig.clip_vit_base_patch16(),
-                       load("clip").clip_config_to_vit_config(transformers.CLIPConfig(vision_config={"patch_size": 16})))):
-        diff = {f.name: (getattr(ref, f.name, "<absent>"), getattr(ours, f.name)) for f in dataclasses.fields(ours)
-                if getattr(ref, f.name, "<absent>") != getattr(ours, f.name)}
+    c = _contracts()
+    for ours, ref in ((ViTConfig.vit_base_patch16_224(), c["vit_conversion/vit_base_patch16_224"]),
+                      (ViTConfig.clip_vit_base_patch16(), c["vit_conversion/clip_vit_base_patch16"])):
+        diff = {f.name: (ref.get(f.name, "<absent>"), getattr(ours, f.name)) for f in dataclasses.fields(ours)
+                if ref.get(f.name, "<absent>") != json.loads(json.dumps(getattr(ours, f.name), default=str))}
         assert diff == {}, diff
 
 

@@ -3,8 +3,8 @@
 dropout_add_layer_norm (fp32 residual for layer 0), swiglu, pad_input -- each bound to the HIP backend through
 contrastors_amd.flash_attn_api.  The composition follows sc/models/encoder/modeling_nomic_bert.py:515-587,307-395,
 sc/layers/block.py:389-463 (post-norm), sc/layers/attention.py:112-135,172-182,243 and sc/layers/mlp.py:68-83 line by line
-(re-declared here because /root/reference does not exist on the GPU box; tests/test_shim_cpu.py imports and constructs the
-reference's own modules on this surface in the build container).  Judged against the fp32 oracle with the reference's
+(re-declared here, so that the test needs nothing outside the repository; tests/test_shim_cpu.py checks that the surface
+exports every name those modules import).  Judged against the fp32 oracle with the reference's
 3 x bf16-eager rule, and against the native engine (the same arithmetic fused into one call)."""
 from types import SimpleNamespace
 
