@@ -66,6 +66,18 @@ class CxChunkBuffers(C.Structure):
     ] + [("ws_floats", i64)] + [(n, vp) for n in ("zf", "hf", "meanf", "rstdf", "patch_in", "patch_proj")] + [("checkpoint", i32), ("drop_active", i32), ("drop_seed", C.c_ulonglong), ("drop_offset", C.c_ulonglong), ("g_d", vp), ("layer_events", C.POINTER(vp)), ("zpre", vp), ("ckpt_keep", i32), ("patch_keep", vp), ("patch_inv", vp), ("n_keep", i32), ("n_patch_all", i32)]
 
 
+
+class CxVitSubLN(C.Structure):
+    _fields_ = [(n, vp) for n in ("norm_g", "norm_b", "gnorm_g", "gnorm_b")]
+
+
+class CxVitExt(C.Structure):
+    """EVA-02 extension of the ViT entry points (include/contrastors_hip.h): 2-D RoPE table, the sub-LN of the MLP, no ln_f."""
+    _fields_ = [("rope_cos", vp), ("rope_sin", vp), ("n_rope", i32), ("n_prefix", i32), ("no_final_ln", i32),
+                ("subln_eps", f32), ("sub_ln", C.POINTER(CxVitSubLN)), ("z", vp), ("zmean", vp), ("zrstd", vp),
+                ("yg_wide", vp)]
+
+
 # name -> (restype, argtypes).  Keep in the order of include/contrastors_hip.h.
 _SIGS = {
     "cx_abi_version": (i32, []),
@@ -149,6 +161,17 @@ _SIGS = {
     "cx_vit_forward_hidden": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, i32, vp, i32, i32, i32, i32, i32,
                                     i32, vp, vp]),
     "cx_vit_backward_hidden": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, i32, i32, vp, vp]),
+    "cx_rope2d_qkv_inplace": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cx_swiglu_subln_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, vp]),
+    "cx_swiglu_subln_bwd": (i32, [vp] * 11 + [i64, i32, i32, vp]),
+    "cx_vit_forward_ex": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), C.POINTER(CxVitExt), vp, i32, vp, i32, i32,
+                                i32, i32, i32, i32, vp, vp]),
+    "cx_vit_backward_ex": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), C.POINTER(CxVitExt), vp, i32, i32, vp, vp,
+                                 vp]),
+    "cx_vit_forward_hidden_ex": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), C.POINTER(CxVitExt), vp, i32, vp, i32,
+                                       i32, i32, i32, i32, i32, vp, vp]),
+    "cx_vit_backward_hidden_ex": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), C.POINTER(CxVitExt), vp, i32, i32,
+                                        vp, vp]),
     "cx_xent_fwd": (i32, [vp, i32, vp, vp, vp, i32, i32, i64, f32, i64, vp]),
     "cx_xent_bwd": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, i64, f32, i64, vp]),
     "cx_grad_sq_norm": (i32, [vp, i64, vp, vp]),

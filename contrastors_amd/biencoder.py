@@ -66,6 +66,13 @@ class LogitScale(torch.nn.Module):
 
 
 def _default_trunk_config(name: str) -> NomicBertConfig:
+    if "eva02" in name:
+        # nomic-ai/vit_eva02_base_patch16_224.mim_in22k (the nomic-embed-vision-v1.5 recipe; sc/models/vit/timm_vit.py:71-95):
+        # B/16 at 224 is the only EVA-02 size built
+        if "vit_eva02_base_patch16_224" not in name:
+            raise ValueError(f"no offline architecture table entry for {name!r}: the EVA-02 tower built is "
+                             "vit_eva02_base_patch16_224; pass BiEncoderConfig.trunk_config")
+        return ViTConfig.eva02_base_patch16_224()
     if "nomic" in name:
         return NomicBertConfig.nomic_bert_2048()
     if "bert-base" in name:

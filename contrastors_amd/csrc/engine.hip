@@ -62,7 +62,26 @@ struct Slots {
     uint16_t* h2(int s) const { return b->h2 + (size_t)(e->prenorm ? sl(s) : sl_in(s)) * T_cap * d; }
     float* mean2(int s) const { return b->mean2 + (size_t)sl(s) * T_cap; }
     float* rstd2(int s) const { return b->rstd2 + (size_t)sl(s) * T_cap; }
+    // EVA-02 sub-LN (CxVitExt): its output (the fc2 input) and statistics follow the slot mapping of act
+    uint16_t* ez(const CxVitExt* x, int s) const { return x->z + (size_t)sl(s) * T_cap * I; }
+    float* ezmean(const CxVitExt* x, int s) const { return x->zmean + (size_t)sl(s) * T_cap; }
+    float* ezrstd(const CxVitExt* x, int s) const { return x->zrstd + (size_t)sl(s) * T_cap; }
 };
+
+// EVA-02 extension of a ViT call (NULL for every other tower): which parts of it are active
+inline bool ext_rope(const CxVitExt* x) { return x && x->rope_cos; }
+inline bool ext_subln(const CxVitExt* x) { return x && x->sub_ln; }
+inline bool ext_no_lnf(const CxVitExt* x) { return x && x->no_final_ln; }
+int check_ext(const CxVitExt* x, const CxEncoderDesc* e, const CxChunkBuffers* b) {
+    if (!x) return CX_OK;
+    if (x->rope_cos && (!x->rope_sin || x->n_rope <= 0 || x->n_prefix < 0)) return CX_ERR_ARG;
+    if (x->sub_ln) {
+        if (!e->gated || !x->z || !x->zmean || !x->zrstd || (!x->yg_wide && !b->g_wide)) return CX_ERR_ARG;
+        for (int l = 0; l < e->n_layer; ++l)
+            if (!x->sub_ln[l].norm_g || !x->sub_ln[l].norm_b) return CX_ERR_ARG;
+    }
+    return CX_OK;
+}
 
 // save: 0 no-grad pass, 1 saving forward / backward (the arena's `checkpoint` / `ckpt_keep` pick the slot mode)
 Slots make_slots(const CxEncoderDesc* enc, const CxChunkBuffers* buf, int save) {
@@ -146,10 +165,20 @@ struct BlockRunner {
     const int32_t* cu_seqlens;
     int Bc, T, max_seqlen;
     void* stream;
+    const CxVitExt* ext = nullptr;
 
     // (`residual`: added to the fc2 / out_proj output in the GEMM epilogue when possible; *folded reports it)
     int mlp_up(const CxLayerWeights& w, const uint16_t* x, int l, bool keep) const {
         const int d = enc->d, I = enc->d_inner;
+        if (ext_subln(ext)) {
+            // EVA-02 (GatedMLP with fc1 biases and norm_layer): biased fc11 || fc12 into the single-slot scratch, then SwiGLU + the
+            // I-wide LayerNorm in one pass; act and the gate stay for backward next to z, which fc2 reads
+            uint16_t* yg = ext->yg_wide ? ext->yg_wide : buf->g_wide;
+            CX_TRY(cx_gemm_bf16_nt(x, w.Wfc1, yg, w.bfc1, T, 2 * I, d, d, d, 2 * I, 0, 1, 1.f, stream));
+            const CxVitSubLN& n = ext->sub_ln[l];
+            return cx_swiglu_subln_fwd(yg, n.norm_g, n.norm_b, keep ? s.yg(l) : nullptr, s.act(l), s.ez(ext, l), s.ezmean(ext, l),
+                                       s.ezrstd(ext, l), T, I, ext->subln_eps, stream);
+        }
         if (enc->gated) {
             // fc11 || fc12 + SwiGLU in one kernel; the gate is only written when backward needs it
             return cx_gemm_bf16_swiglu_gate(x, w.Wfc1, keep ? s.yg(l) : nullptr, s.act(l), T, I, d, d, d, I, I, stream);
@@ -165,11 +194,14 @@ struct BlockRunner {
     int mlp(const CxLayerWeights& w, const uint16_t* x, int l, uint16_t* out, const uint16_t* residual, bool keep,
             bool* folded) const {
         CX_TRY(mlp_up(w, x, l, keep));
-        return proj_residual(s.act(l), w.Wfc2, w.bfc2, residual, out, T, enc->d, enc->d_inner, folded, stream, buf);
+        return proj_residual(ext_subln(ext) ? s.ez(ext, l) : s.act(l), w.Wfc2, w.bfc2, residual, out, T, enc->d, enc->d_inner, folded, stream, buf);
     }
     int attn(const CxLayerWeights& w, const uint16_t* x, int l, uint16_t* out, const uint16_t* residual, bool* folded) const {
         const int d = enc->d;
         CX_TRY(cx_gemm_bf16_nt(x, w.Wqkv, s.qkv(l), w.bqkv, T, 3 * d, d, d, d, 3 * d, 0, 1, 1.f, stream));
+        if (ext_rope(ext))   // EVA-02: 2-D RoPE on q / k in place; the saved qkv is the rotated one (the backward knows)
+            CX_TRY(cx_rope2d_qkv_inplace(s.qkv(l), cu_seqlens, ext->rope_cos, ext->rope_sin, ext->n_rope, Bc, enc->n_head, T,
+                                         ext->n_prefix, 1, stream));
         if (buf->drop_active && enc->attn_pdrop > 0.f) {  // dropout sites of a chunk: 2l, 2l+1 residual, 2L embeddings, 2L+1+l attention
             CX_TRY(cx_attn_varlen_dropout_fwd(s.qkv(l), cu_seqlens, enc->rot_cos, enc->rot_sin, s.ctx(l), s.lse(l), Bc,
                                               enc->n_head, T, max_seqlen, enc->softmax_scale, enc->attn_pdrop, buf->drop_seed,
@@ -243,9 +275,9 @@ struct BlockRunner {
 
 int blocks_forward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Slots& s, const uint16_t* h0,
                    const int32_t* cu_seqlens, int Bc, int T, int max_seqlen, int save, const uint16_t** h_final,
-                   void* stream) {
+                   void* stream, const CxVitExt* ext = nullptr) {
     const int d = enc->d, L = enc->n_layer;
-    const BlockRunner run{enc, buf, s, cu_seqlens, Bc, T, max_seqlen, stream};
+    const BlockRunner run{enc, buf, s, cu_seqlens, Bc, T, max_seqlen, stream, ext};
     // (checkpointing: a recomputed block keeps only its input, by the slot mapping; the blocks above first_kept keep all)
     if (!enc->prenorm) {
         const uint16_t* h_in = h0;
@@ -256,7 +288,7 @@ int blocks_forward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Sl
         *h_final = h_in;
         return CX_OK;
     }
-    if (!buf->zf || !buf->hf || !buf->meanf || !buf->rstdf || !enc->lnf_g || !enc->lnf_b) return CX_ERR_ARG;
+    if (!buf->zf || !buf->hf || !buf->meanf || !buf->rstdf || (!ext_no_lnf(ext) && (!enc->lnf_g || !enc->lnf_b))) return CX_ERR_ARG;
     if (buf->drop_active && enc->resid_pdrop > 0.f) return CX_ERR_ARG;   // dropout: post-norm text trunks only
     const uint16_t* x = h0;        // output of the previous sub-layer (the embeddings for the first block)
     const uint16_t* r = nullptr;   // residual stream
@@ -265,6 +297,11 @@ int blocks_forward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Sl
         CX_TRY(run.pre_block(l, x, r, r_folded, save != 0 && s.kept(l), false, &x, &r, &r_folded));
         // checkpointing keeps ONE tensor per block, the complete residual stream z1(l): needs the fc2 epilogue fold
         if (save == 2 && !r_folded) return CX_ERR_SHAPE;
+    }
+    if (ext_no_lnf(ext)) {   // EVA-02 (sc/models/vit/vit.py:263-273): the hidden states are the residual stream itself
+        if (!r_folded || x != buf->zf) return CX_ERR_SHAPE;   // (the fc2 epilogue folds the residual for every shape it serves)
+        *h_final = buf->zf;
+        return CX_OK;
     }
     CX_TRY(cx_layernorm_fwd(x, r, enc->lnf_g, enc->lnf_b, buf->hf, r_folded ? nullptr : buf->zf, buf->meanf, buf->rstdf, T,
                             d, enc->ln_eps, stream));
@@ -278,7 +315,8 @@ int check_bwd_buffers(const CxChunkBuffers* buf) {
 }
 
 // The natural-layout wgrad kernel reduces over round_up(T,64) token rows: clear the pad rows of every operand.
-int clear_pad_rows(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Slots& s, int T, void* stream) {
+int clear_pad_rows(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Slots& s, int T, void* stream,
+                   const CxVitExt* ext = nullptr) {
     const int Tp = (int)round_up(T, 64);
     if (Tp == T) return CX_OK;
     const int d = enc->d, I = enc->d_inner, L = enc->n_layer;
@@ -298,6 +336,7 @@ int clear_pad_rows(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Sl
         CX_TRY(clear(s.h1(l), d));
         CX_TRY(clear(s.ctx(l), d));
         CX_TRY(clear(s.h2(l), d));
+        if (ext_subln(ext)) CX_TRY(clear(s.ez(ext, l), I));   // (the fc2 wgrad reads z)
     }
     return CX_OK;
 }
@@ -315,7 +354,8 @@ struct PooledGrad {
 // ---- transformer blocks, backward.  In: gradient of the final hidden states in buf->g_a (or `pg`, see above).  Out: the
 // gradient of the input embeddings as the sum of *da and *db (db may come back NULL). ---------------------------------
 int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const Slots& s, const int32_t* cu_seqlens, int Bc,
-                    int T, int max_seqlen, const PooledGrad* pg, const uint16_t** da_out, const uint16_t** db_out, void* stream) {
+                    int T, int max_seqlen, const PooledGrad* pg, const uint16_t** da_out, const uint16_t** db_out, void* stream,
+                    const CxVitExt* ext = nullptr) {
     const int d = enc->d, I = enc->d_inner, H = enc->n_head, L = enc->n_layer;
     // MLP backward: dm -> gradients of fc2 / fc1 parameters, d(mlp input) into buf->g_b
     // `add` (optional): the residual-branch gradient that the following LayerNorm backward would add to this dgrad
@@ -324,6 +364,16 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
     auto mlp_bwd = [&](const CxLayerWeights& w, int l, const uint16_t* dm, const uint16_t* mlp_in, const uint16_t* add,
                        bool* folded, bool bias_done) -> int {
         if (w.gbfc2 && !bias_done) CX_TRY(cx_bias_grad(dm, w.gbfc2, T, d, d, stream));
+        if (ext_subln(ext)) {
+            // EVA-02: fc2 on z; dz -> sub-LN backward -> SwiGLU backward -> dYG (+ d gamma, d beta, the fc1 bias gradient) in one pass
+            CX_TRY(wgrad(dm, d, s.ez(ext, l), I, w.gWfc2, buf, T, stream));
+            CX_TRY(cx_gemm_bf16_nt(dm, w.Wfc2T, buf->g_act, nullptr, T, I, d, d, d, I, 0, 1, 1.f, stream));
+            const CxVitSubLN& n = ext->sub_ln[l];
+            CX_TRY(cx_swiglu_subln_bwd(buf->g_act, s.act(l), s.yg(l), s.ezmean(ext, l), s.ezrstd(ext, l), n.norm_g, buf->g_wide,
+                                       n.gnorm_g, n.gnorm_b, w.gbfc1, buf->ws_f32, buf->ws_floats, T, I, stream));
+            CX_TRY(wgrad(buf->g_wide, s.wfc1, mlp_in, d, w.gWfc1, buf, T, stream));
+            return proj_residual(buf->g_wide, w.Wfc1T, nullptr, add, buf->g_b, T, d, s.wfc1, folded, stream, buf);
+        }
         CX_TRY(wgrad(dm, d, s.act(l), I, w.gWfc2, buf, T, stream));
         int fused = CX_ERR_SHAPE;
         if (enc->gated)  // fc2 dgrad + SwiGLU backward in one kernel: d(act) never touches HBM
@@ -370,6 +420,9 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
             CX_TRY(cx_attn_varlen_bwd(buf->g_b, s.qkv(l), s.ctx(l), s.lse(l), cu_seqlens, enc->rot_cos, enc->rot_sin,
                                       buf->delta, buf->g_wide, Bc, H, T, max_seqlen, enc->softmax_scale, stream));
         }
+        if (ext_rope(ext))   // EVA-02: dq / dk through the inverse rotation (dv untouched)
+            CX_TRY(cx_rope2d_qkv_inplace(buf->g_wide, cu_seqlens, ext->rope_cos, ext->rope_sin, ext->n_rope, Bc, H, T, ext->n_prefix,
+                                         -1, stream));
         if (w.gbqkv) CX_TRY(cx_bias_grad(buf->g_wide, w.gbqkv, T, 3 * d, 3 * d, stream));
         CX_TRY(wgrad(buf->g_wide, 3 * d, attn_in, d, w.gWqkv, buf, T, stream));
         return proj_residual(buf->g_wide, w.WqkvT, nullptr, add, buf->g_b, T, d, 3 * d, folded, stream, buf);
@@ -392,7 +445,7 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
     };
     // activation checkpointing (slot mode 2): the block's intermediates are recomputed from its saved input into slot 0
     // right before its backward (bit-identical: every kernel on the path is deterministic)
-    const BlockRunner run{enc, buf, s, cu_seqlens, Bc, T, max_seqlen, stream};
+    const BlockRunner run{enc, buf, s, cu_seqlens, Bc, T, max_seqlen, stream, ext};
     if (!enc->prenorm) {
         const uint16_t* da = buf->g_a;
         const uint16_t* db = nullptr;
@@ -458,7 +511,13 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
     // ln_f, then of each block's LN1) is the gradient of the fc2 output of the block BELOW it in the loop, g_a (= dz of LN2)
     // that of the out_proj output of the same block: their column sums are those bias gradients.
     bool bias_c_done = false;   // "the kernel that wrote g_c accumulated layers[l].gbfc2"
-    {
+    if (ext_no_lnf(ext)) {
+        // no final LayerNorm: the gradient of the hidden states (g_a) IS the gradient of the last residual stream
+        if (pg) return CX_ERR_ARG;
+        if (hipMemcpyAsync(buf->g_c, buf->g_a, (size_t)T * d * sizeof(uint16_t), hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+            hipSuccess)
+            return CX_ERR_LAUNCH;
+    } else {
         float* gb_top = enc->layers[L - 1].gbfc2;
         if (pg) {
             const bool cs = gb_top && buf->ws_f32 && buf->ws_floats >= 3L * d * 256;
@@ -500,7 +559,7 @@ namespace {
 // the final hidden states themselves (hidden_out, (T, d) bf16 after ln_f)
 int vit_forward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const void* pixels, int pixels_bf16,
                      const int32_t* cu_seqlens, int Bc, int Cc, int H, int W, int patch, int save_for_backward, float* emb_out,
-                     uint16_t* hidden_out, void* stream) {
+                     uint16_t* hidden_out, void* stream, const CxVitExt* ext = nullptr) {
     if (Bc <= 0) return CX_OK;
     if (!enc || !buf || patch <= 0 || (H % patch) || (W % patch)) return CX_ERR_ARG;
     // PatchDropout (CxChunkBuffers.patch_keep): only the kept patches of every image exist from here on
@@ -511,6 +570,8 @@ int vit_forward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const 
     CX_TRY(check_desc(enc, buf, T));
     if (!enc->Wpatch || !enc->cls_token || !enc->vit_pos || !buf->patch_in || !buf->patch_proj) return CX_ERR_ARG;
     if (enc->patch_dim != Cc * patch * patch || (enc->patch_dim % 64) != 0) return CX_ERR_SHAPE;
+    CX_TRY(check_ext(ext, enc, buf));
+    if (ext_rope(ext) && (keep || P > ext->n_rope)) return CX_ERR_ARG;   // (the table rotates the full patch grid only)
     (void)hipGetLastError();
     const int d = enc->d, I = enc->d_inner;
     const Slots s = make_slots(enc, buf, save_for_backward);
@@ -526,7 +587,7 @@ int vit_forward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const 
         CX_TRY(cx_vit_assemble_fwd_gather(buf->patch_proj, enc->cls_token, enc->vit_pos, buf->h0, Bc, P, d, keep, stream));
     }
     const uint16_t* h_final = nullptr;
-    CX_TRY(blocks_forward(enc, buf, s, buf->h0, cu_seqlens, Bc, T, S, s.mode, &h_final, stream));
+    CX_TRY(blocks_forward(enc, buf, s, buf->h0, cu_seqlens, Bc, T, S, s.mode, &h_final, stream, ext));
     if (hidden_out)
         return hipMemcpyAsync(hidden_out, h_final, (size_t)T * d * sizeof(uint16_t), hipMemcpyDeviceToDevice,
                               (hipStream_t)stream) == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
@@ -535,19 +596,21 @@ int vit_forward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const 
 }
 
 int vit_backward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int32_t* cu_seqlens, int Bc, int n_patch,
-                      const float* demb, const float* emb_out, const uint16_t* dhidden, void* stream) {
+                      const float* demb, const float* emb_out, const uint16_t* dhidden, void* stream,
+                      const CxVitExt* ext = nullptr) {
     if (Bc <= 0) return CX_OK;
     if (!enc || !buf || n_patch <= 0) return CX_ERR_ARG;
     const int P = n_patch, S = P + 1, T = Bc * S;
     CX_TRY(check_desc(enc, buf, T));
     if ((!dhidden && (!demb || !emb_out)) || !buf->patch_in || !buf->patch_proj) return CX_ERR_ARG;
     CX_TRY(check_bwd_buffers(buf));
+    CX_TRY(check_ext(ext, enc, buf));
     (void)hipGetLastError();
     const int d = enc->d, I = enc->d_inner;
     const Slots s = make_slots(enc, buf, 1);
-    CX_TRY(clear_pad_rows(enc, buf, s, T, stream));
+    CX_TRY(clear_pad_rows(enc, buf, s, T, stream, ext));
     const PooledGrad pg{demb, emb_out, buf->pool_norm, enc->pool_mode, enc->normalize};
-    const bool fold_pool = !dhidden && enc->prenorm && (enc->pool_mode == 0 || enc->pool_mode == 1);   // (see cx_encoder_backward)
+    const bool fold_pool = !dhidden && enc->prenorm && !ext_no_lnf(ext) && (enc->pool_mode == 0 || enc->pool_mode == 1);   // (see cx_encoder_backward)
     if (dhidden) {
         if (hipMemcpyAsync(buf->g_a, dhidden, (size_t)T * d * sizeof(uint16_t), hipMemcpyDeviceToDevice,
                            (hipStream_t)stream) != hipSuccess)
@@ -558,7 +621,7 @@ int vit_backward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const
     }
     const uint16_t* da = nullptr;
     const uint16_t* db = nullptr;
-    CX_TRY(blocks_backward(enc, buf, s, cu_seqlens, Bc, T, S, fold_pool ? &pg : nullptr, &da, &db, stream));
+    CX_TRY(blocks_backward(enc, buf, s, cu_seqlens, Bc, T, S, fold_pool ? &pg : nullptr, &da, &db, stream, ext));
     if (db) return CX_ERR_ARG;  // (post-norm ViT would need the two branches summed first; no such model family)
     if (enc->lnpre_g) {   // through the pre-LayerNorm: da (= g_c) -> g_a
         if (!buf->zpre) return CX_ERR_ARG;
@@ -738,6 +801,34 @@ int cx_vit_backward_hidden(const CxEncoderDesc* enc, const CxChunkBuffers* buf, 
                            const uint16_t* dhidden, void* stream) {
     if (Bc > 0 && !dhidden) return CX_ERR_ARG;
     return vit_backward_impl(enc, buf, cu_seqlens, Bc, n_patch, nullptr, nullptr, dhidden, stream);
+}
+
+// ---- the same four with the EVA-02 extension (CxVitExt; NULL = the calls above) -------------------------------------
+int cx_vit_forward_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const void* pixels,
+                      int pixels_bf16, const int32_t* cu_seqlens, int Bc, int Cc, int H, int W, int patch, int save_for_backward,
+                      float* emb_out, void* stream) {
+    if (Bc > 0 && !emb_out) return CX_ERR_ARG;
+    return vit_forward_impl(enc, buf, pixels, pixels_bf16, cu_seqlens, Bc, Cc, H, W, patch, save_for_backward, emb_out, nullptr,
+                            stream, ext);
+}
+
+int cx_vit_backward_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const int32_t* cu_seqlens, int Bc,
+                       int n_patch, const float* demb, const float* emb_out, void* stream) {
+    return vit_backward_impl(enc, buf, cu_seqlens, Bc, n_patch, demb, emb_out, nullptr, stream, ext);
+}
+
+int cx_vit_forward_hidden_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const void* pixels,
+                             int pixels_bf16, const int32_t* cu_seqlens, int Bc, int Cc, int H, int W, int patch,
+                             int save_for_backward, uint16_t* hidden_out, void* stream) {
+    if (Bc > 0 && !hidden_out) return CX_ERR_ARG;
+    return vit_forward_impl(enc, buf, pixels, pixels_bf16, cu_seqlens, Bc, Cc, H, W, patch, save_for_backward, nullptr, hidden_out,
+                            stream, ext);
+}
+
+int cx_vit_backward_hidden_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const int32_t* cu_seqlens,
+                              int Bc, int n_patch, const uint16_t* dhidden, void* stream) {
+    if (Bc > 0 && !dhidden) return CX_ERR_ARG;
+    return vit_backward_impl(enc, buf, cu_seqlens, Bc, n_patch, nullptr, nullptr, dhidden, stream, ext);
 }
 
 int cx_abi_version(void) { return 10; }  // 10: cx_gemm_bf16_act_bwd; 9: cx_infonce_fwd_argmax; 8: cx_cast_transpose_f32_to_bf16_batched / CxCastJob; 7: CxChunkBuffers.patch_keep / patch_inv / n_keep (PatchDropout);  // 2: CxChunkBuffers.checkpoint; 3: dropout state, sorted embedding backward; 4: CxEncoderDesc.attn_pdrop; 5: CxChunkBuffers.layer_events, cx_layernorm_bwd_pooled; 6: CxChunkBuffers.ckpt_keep

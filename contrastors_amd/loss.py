@@ -400,6 +400,8 @@ def _arena_bytes_per_token(tower) -> float:
     d, I, L = cfg.n_embd, cfg.n_inner, cfg.n_layer
     wfc1 = 2 * I if getattr(cfg, "gated", False) else I
     per_layer = 2 * (3 * d + 5 * d + I + I) + 4 * (cfg.n_head + 4)   # (the gated MLP keeps the gate alone: (T, I), not (T, 2I))
+    if getattr(cfg, "norm_mlp", False):   # EVA-02: the MLP LayerNorm's output and statistics per slot
+        per_layer += 2 * I + 4 * 2
     kept = 1 if getattr(tower.trunk, "gradient_checkpointing", False) else L
     needs_tr = any(f % 256 for f in (d, 3 * d, I, wfc1))   # (the transposed wgrad operands: nomic_bert._ChunkArena)
     scratch = 2 * (3 * d + (3 if needs_tr else 1) * max(3 * d, wfc1) + I)

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 from .flash_attn_api.flash_attn_interface import flash_attn_kvpacked_func
+from .flash_attn_api.ops.activations import swiglu
 from .flash_attn_api.ops.fused_dense import FusedDense
 
 
@@ -57,18 +58,34 @@ class _PoolingMLP(torch.nn.Module):
         return self.fc2(F.gelu(y.float()).to(y.dtype))
 
 
+class _PoolingGatedMLP(torch.nn.Module):
+    """The head of a SwiGLU tower (EVA-02): GatedMLP without its norm (modeling_biencoder.py:107-115, sc/layers/mlp.py:37-83):
+    fc2(swiglu(fc12 x, fc11 x)), hidden width rounded up to a multiple of 256 as GatedMLP does."""
+
+    def __init__(self, d: int, inner: int, bias1: bool, bias2: bool, device=None):
+        super().__init__()
+        inner = (inner + 255) // 256 * 256
+        self.fc11 = FusedDense(d, inner, bias=bias1, device=device)
+        self.fc12 = FusedDense(d, inner, bias=bias1, device=device)
+        self.fc2 = FusedDense(inner, d, bias=bias2, device=device)
+
+    def forward(self, x):
+        return self.fc2(swiglu(self.fc12(x), self.fc11(x)))
+
+
 class MultiHeadAttentionPooling(torch.nn.Module):
     def __init__(self, config, device=None):
         super().__init__()
         act = getattr(config, "activation_function", "gelu")
-        if act not in ("gelu", "gelu_new", "gelu_fast", "gelu_pytorch_tanh"):
-            raise NotImplementedError(f"attention pooling with activation {act!r} (gated / quick_gelu heads are not built)")
+        if act not in ("gelu", "gelu_new", "gelu_fast", "gelu_pytorch_tanh", "swiglu"):
+            raise NotImplementedError(f"attention pooling with activation {act!r} (glu / quick_gelu heads are not built)")
         if getattr(config, "use_rms_norm", False):
             raise NotImplementedError("attention pooling with RMSNorm")
         d = config.n_embd
         self.attn = _PoolingAttention(d, config.n_head, bool(getattr(config, "qkv_proj_bias", True)), device=device)
-        self.mlp = _PoolingMLP(d, config.n_inner, bool(getattr(config, "mlp_fc1_bias", True)),
-                               bool(getattr(config, "mlp_fc2_bias", True)), device=device)
+        mlp_cls = _PoolingGatedMLP if act == "swiglu" else _PoolingMLP
+        self.mlp = mlp_cls(d, config.n_inner, bool(getattr(config, "mlp_fc1_bias", True)),
+                           bool(getattr(config, "mlp_fc2_bias", True)), device=device)
         self.norm1 = torch.nn.LayerNorm(d, eps=config.layer_norm_epsilon, device=device)
 
     def forward(self, hidden_states: torch.Tensor, input_ids=None, attention_mask=None) -> torch.Tensor:

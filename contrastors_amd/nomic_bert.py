@@ -180,6 +180,12 @@ class _ChunkArena:
             t["patch_proj"] = torch.empty(T_cap, d, **bf)
         if getattr(cfg, "prepre_layernom", False):  # CLIP flavour: the pre-LayerNorm's input, kept for its backward
             t["zpre"] = torch.empty(T_cap, d, **bf)
+        if getattr(cfg, "norm_mlp", False):  # EVA-02 (CxVitExt): the MLP LayerNorm's output and statistics, per slot like act
+            t["sub_z"] = torch.empty(n_slots, T_cap, I, **bf)
+            t["sub_mean"] = torch.empty(n_slots, T_cap, **f32)
+            t["sub_rstd"] = torch.empty(n_slots, T_cap, **f32)
+            if not with_backward:   # the biased fc1 output's scratch; a backward arena lends its g_wide
+                t["yg_wide"] = torch.empty(T_cap, 2 * I, **bf)
         # split-K workspace (fp32 partial slabs): 8 slabs of the largest weight, 16 of the smallest, for the wgrad GEMMs; every
         # arena has it, because the few-tile long-K projections of SMALL chunks take a split-K route too
         # (cx_gemm_bf16_nt_splitk) and a no-grad forward must round exactly like the saving forward of the same chunk
@@ -229,7 +235,8 @@ class _ChunkArena:
         checkpointing): qkv, ctx, lse, three of z1 / h1 / z2 / h2 (the fourth is the per-layer input tensor a checkpointing
         arena holds anyway), the LayerNorm statistics, the fc1 pre-activation and the activation."""
         d, I, H = cfg.n_embd, cfg.n_inner, cfg.n_head
-        return 2 * (3 * d + d + 3 * d + I + I) + 4 * (H + 4)
+        extra = 2 * I + 4 * 2 if getattr(cfg, "norm_mlp", False) else 0   # EVA-02: the sub-LN output and its statistics
+        return 2 * (3 * d + d + 3 * d + I + I) + 4 * (H + 4) + extra
 
 
 _FULL_CACHE: Dict[tuple, tuple] = {}

@@ -77,6 +77,9 @@ def _load_initial_weights(model: BiEncoder, ma, explicit_arch: bool):
             if "trunk_config" in cfg:  # written by BiEncoder.save_pretrained
                 model.load_pretrained(name)
                 return
+        if getattr(model, "is_vision", False) and getattr(model.trunk.config, "eva", False):
+            load_timm_eva02(model.trunk, name)
+            return
         from transformers import BertConfig
 
         from .hf_bert import load_hf_bert
@@ -94,6 +97,28 @@ def _load_initial_weights(model: BiEncoder, ma, explicit_arch: bool):
     raise FileNotFoundError(
         f"model_args.pretrained is true but {name!r} is not a local directory (no hub access): point model_name / "
         "checkpoint at local weights, or set pretrained: false to train from a random init")
+
+
+def load_timm_eva02(trunk, path: str):
+    """A local directory holding a timm-keyed EVA-02 checkpoint (model.safetensors or pytorch_model.bin) into an EVA-02 image
+    trunk, through the remap of sc/models/vit/timm_vit.py:170-251 (vit.remap_timm_eva02_state_dict).  Every key has to land on
+    a parameter of the tower and every parameter has to be present: anything else raises."""
+    import os
+
+    from .vit import remap_timm_eva02_state_dict
+
+    st = os.path.join(path, "model.safetensors")
+    if os.path.exists(st):
+        from safetensors.torch import load_file
+
+        sd = load_file(st)
+    else:
+        sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu")
+    mapped = remap_timm_eva02_state_dict(sd, trunk.config)
+    unknown = sorted(set(mapped) - set(trunk.reference_state_dict()))
+    if unknown:
+        raise KeyError(f"{path}: checkpoint keys the EVA-02 tower has no parameter for: {unknown[:8]}")
+    trunk.load_reference_state_dict(mapped, strict=True)
 
 
 def _accumulation_steps(ta) -> int:

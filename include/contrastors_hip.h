@@ -548,6 +548,60 @@ int cx_vit_forward_hidden(const CxEncoderDesc* enc, const CxChunkBuffers* buf, c
 int cx_vit_backward_hidden(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int32_t* cu_seqlens, int Bc, int n_patch,
                            const uint16_t* dhidden, void* stream);
 
+/* ---- EVA-02 image tower (sc/models/vit/timm_vit.py:71-95 `vit_eva02_base_patch16_224`, the image tower of the
+ *      nomic-embed-vision-v1.5 recipe): 2-D RoPE on q / k, SwiGLU with fc1 biases and a LayerNorm inside the MLP, no final
+ *      LayerNorm.  Additive to ABI 10: the plain ViT entry points above are unchanged. ----------------------------------
+ * cx_rope2d_qkv_inplace: rotates q and k of a packed (T, 3 * n_head * 64) bf16 qkv in place, interleaved pairs (2j, 2j+1)
+ *   (RotaryEmbeddingCat / apply_rot_embed_cat, sc/layers/embedding.py:297-360): x * cos + rot(x) * sin, rot(x) = (-x1, x0),
+ *   fp32 math, one rounding.  Token t of sequence b (cu_seqlens[b] <= t < cu_seqlens[b + 1]) at offset s uses row s - n_prefix
+ *   of the fp32 (n_rope, 32) tables; offsets < n_prefix (the [cls] token) and rows >= n_rope stay untouched, V always.
+ *   sign = -1: the inverse rotation = the backward on dq / dk of a (T, 3d) gradient buffer. */
+int cx_rope2d_qkv_inplace(uint16_t* qkv, const int32_t* cu_seqlens, const float* rope_cos, const float* rope_sin, int n_rope,
+                          int B, int n_head, int T, int n_prefix, int sign, void* stream);
+/* GatedMLP with norm_layer (sc/layers/mlp.py:37-83): yg (T, 2I) = the BIASED fc1 output in the interleaved-by-32 layout of the
+ * fused fc1 weight; act = bf16(silu(gate) * y) (T, I), gate (T, I) plain column order (may be NULL: the no-grad pass), z =
+ * bf16(LN(act) * gamma + beta) (T, I), mean / rstd (T) fp32 over the whole I-wide row.  I % 256 == 0 and I <= 4096
+ * (CX_ERR_SHAPE otherwise). */
+int cx_swiglu_subln_fwd(const uint16_t* yg, const float* gamma, const float* beta, uint16_t* gate, uint16_t* act, uint16_t* z,
+                        float* mean, float* rstd, int T, int I, float eps, void* stream);
+/* dz (T, I) = gradient of z -> dyg (T, 2I) interleaved; dgamma / dbeta (I) and dbias (2I, interleaved = the fused fc1 bias)
+ * accumulate (+=; each may be NULL).  Per-block fp32 partials in ws (>= 4 I floats, up to 1024 x 4 I used) and a fixed-order
+ * reduction: deterministic, no atomics.  Same shape rule as the forward. */
+int cx_swiglu_subln_bwd(const uint16_t* dz, const uint16_t* act, const uint16_t* gate, const float* mean, const float* rstd,
+                        const float* gamma, uint16_t* dyg, float* dgamma, float* dbeta, float* dbias, float* ws, long ws_floats,
+                        int T, int I, void* stream);
+
+typedef struct CxVitSubLN {
+    const float* norm_g; const float* norm_b;   /* mlp.norm.weight / .bias, fp32 (I) */
+    float* gnorm_g; float* gnorm_b;             /* their gradient accumulators (may be NULL) */
+} CxVitSubLN;
+
+/* What a block of the EVA-02 tower adds to CxEncoderDesc / CxChunkBuffers.  The host refreshes the arena pointers before each
+ * call (the library reads the struct only while it enqueues). */
+typedef struct CxVitExt {
+    const float* rope_cos; const float* rope_sin;   /* fp32 (n_rope, 32) per patch, or NULL: no rotary */
+    int n_rope, n_prefix;                           /* table rows; leading tokens not rotated ([cls]: 1) */
+    int no_final_ln;                                /* != 0: hidden states = the residual stream after the last block */
+    float subln_eps;                                /* eps of the LayerNorm inside the MLP (nn.LayerNorm default 1e-5) */
+    const CxVitSubLN* sub_ln;                       /* HOST array of n_layer, or NULL: no sub-LN (the plain MLP path) */
+    /* arena: per-layer slots (slot stride T_cap rows, the slot mapping of yg / act, single slot under checkpointing) */
+    uint16_t* z;                                    /* (slots, T_cap, I) bf16 sub-LN output (the fc2 input) */
+    float* zmean; float* zrstd;                     /* (slots, T_cap) */
+    uint16_t* yg_wide;                              /* (T_cap, 2I) bf16 scratch for the biased fc1 output; NULL = g_wide */
+} CxVitExt;
+
+/* The four ViT entry points with an extension; ext == NULL is exactly the call without the suffix. */
+int cx_vit_forward_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const void* pixels,
+                      int pixels_bf16, const int32_t* cu_seqlens, int Bc, int C, int H, int W, int patch, int save_for_backward,
+                      float* emb_out, void* stream);
+int cx_vit_backward_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const int32_t* cu_seqlens, int Bc,
+                       int n_patch, const float* demb, const float* emb_out, void* stream);
+int cx_vit_forward_hidden_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const void* pixels,
+                             int pixels_bf16, const int32_t* cu_seqlens, int Bc, int Cc, int H, int W, int patch,
+                             int save_for_backward, uint16_t* hidden_out, void* stream);
+int cx_vit_backward_hidden_ex(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const CxVitExt* ext, const int32_t* cu_seqlens,
+                              int Bc, int n_patch, const uint16_t* dhidden, void* stream);
+
 /* ---- K12  fused softmax cross-entropy over a vocabulary-sized class axis (flash_attn.losses.cross_entropy.
  *      CrossEntropyLoss, csrc/xentropy; sc/models/encoder/modeling_nomic_bert.py:603-610).  logits: (N, V) bf16
  *      (logits_bf16 != 0) or fp32, row stride ld; labels int64[N] (== ignore_index -> loss 0, zero gradient).
