@@ -1,0 +1,325 @@
+// search.hip -- exact inner-product top-k search (faiss IndexFlatIP.search) for the data-curation stage: consistency
+// filtering (scripts/text/index_filtering.py:363-391) and hard-negative mining (scripts/text/get_negatives.py:111-196,
+// scripts/text/mine_beir_negatives_full.py:98-136).  The (M x N) score matrix is never written.
+//
+// Stage 1 (search_tiles_kernel): a workgroup owns one 128-query tile and walks a contiguous range of 128-document tiles
+// (its "split" of the corpus).  Scores are bf16 x bf16 -> fp32 on v_mfma_f32_16x16x32_bf16, issued as (A := document rows,
+// B := query rows) so that a lane owns one query per 16-block.  Each query row keeps a sorted running top-k list of its
+// split in the workspace and its current k-th best score in LDS; the epilogue compares every score with that threshold in
+// registers and only rows with a score above it (and below the row's bound) go through the insert path, which gathers the
+// tile's admissible candidates, drops the row's excluded ids, ranks them and merges them into the list by rank counting.
+// Stage 2 (merge_splits_kernel): per row, every list entry's final rank = its rank in its own list + the number of entries
+// of the other lists that beat it (binary search); ranks are unique, so the merge is a scatter with no atomics.
+//
+// Order: descending score, ties to the lower id -- a strict total order on (score, id).  Every score has ONE instruction
+// sequence (the same K order whatever tile or split it falls in), so the result is the unique top-k of that order and is
+// bit-identical for any split count.  Rows with fewer than k admissible documents are padded with (-inf, -1).
+#include "cx_common.h"
+#include "../../include/contrastors_hip.h"
+
+namespace {
+
+constexpr int TM = 128, TN = 128, BK = 64;
+constexpr int PANEL = TM * BK * 2;   // 16 KiB: one operand's 64-wide K chunk, 128 rows x 128 B
+constexpr int MAXK = 1024;
+constexpr int MAXSPLIT = 64;
+// column indices are int: the last tile's columns reach N + TN - 2, which must not overflow
+constexpr long MAX_N = 0x7fffffffL - TN;
+constexpr int SPLIT_TARGET_WG = 512; // auto split: (M-tile, split) workgroups for two waves of the 256 CUs
+
+struct Cand {
+    float s;
+    int id;
+};
+
+CX_DEVICE bool beats(Cand a, Cand b) { return a.s > b.s || (a.s == b.s && a.id < b.id); }
+
+// [128 rows][8 chunks of 16 B]: chunk c of row r at r*128 + ((c ^ (r & 7)) << 4)
+CX_DEVICE int poff(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
+
+// LDS writes / global stores of this wave are complete and visible to the wave's later reads (no compiler reordering)
+CX_DEVICE void wave_sync() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+struct SearchParams {
+    const bf16_t* Q;
+    const bf16_t* D;
+    long ldq, ldd;
+    int M, N, d, k;
+    int nsplit, tiles_n, tiles_per_split;
+    const int64_t* xptr;   // (M + 1) CSR row pointers into xids (absolute), or null
+    const int64_t* xids;
+    const float* below;    // (M) exclusive upper bound on the score, or null
+    Cand* lists;           // (M, nsplit, k)
+    int* counts;           // (M, nsplit)
+};
+
+CX_DEVICE void stage(const SearchParams& p, int m0, int n0, int k0, int tid, uint4 (&sq)[4], uint4 (&sd)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int item = tid + 256 * i, r = item >> 3, c = item & 7;
+        const int gm = min(m0 + r, p.M - 1), gn = min(n0 + r, p.N - 1);   // clamped rows are read but never admitted
+        sq[i] = *reinterpret_cast<const uint4*>(p.Q + (int64_t)gm * p.ldq + k0 + c * 8);
+        sd[i] = *reinterpret_cast<const uint4*>(p.D + (int64_t)gn * p.ldd + k0 + c * 8);
+    }
+}
+CX_DEVICE void commit(char* qbuf, char* dbuf, int tid, const uint4 (&sq)[4], const uint4 (&sd)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int item = tid + 256 * i, r = item >> 3, c = item & 7;
+        *reinterpret_cast<uint4*>(qbuf + poff(r, c)) = sq[i];
+        *reinterpret_cast<uint4*>(dbuf + poff(r, c)) = sd[i];
+    }
+}
+
+// number of entries of the sorted list L[0 .. n) that beat e
+CX_DEVICE int count_beating(const Cand* L, int n, Cand e) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (beats(L[mid], e)) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct SearchLds {
+    char ops[4 * PANEL];          // [Q, D] x 2 K-chunk buffers; after the K loop: the 128 x 128 fp32 score tile
+    Cand mbuf[4][MAXK];           // per wave: the merged list being built
+    Cand cand[4][TN];             // per wave: the tile's admissible candidates of one row, in column order
+    Cand sorted[4][TN];           // ... and ranked
+    float thr[TM], bel[TM];
+    int cnt[TM], flag[TM];
+    int any;
+};
+
+// one wave: insert the admissible scores of tile row `row` (scores in `tile`) into the row's running list
+CX_DEVICE void insert_row(const SearchParams& p, SearchLds& L, const float* tile, int row, int m, int n0, int split, int wave,
+                          int lane) {
+    const float thr = L.thr[row], bel = L.bel[row];
+    const int cnt = L.cnt[row];
+    const int64_t x0 = p.xptr ? p.xptr[m] : 0, x1 = p.xptr ? p.xptr[m + 1] : 0;
+    Cand* cand = L.cand[wave];
+    Cand* srt = L.sorted[wave];
+    Cand* mb = L.mbuf[wave];
+    int c = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int j = lane + 64 * h, n = n0 + j;
+        const float s = tile[row * TN + j];
+        bool ok = n < p.N && s > thr && s < bel;
+        if (ok)
+            for (int64_t e = x0; e < x1; ++e)
+                if (p.xids[e] == n) ok = false;
+        const unsigned long long mask = __ballot(ok);
+        const int pos = c + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+        if (ok) cand[pos] = Cand{s, n};
+        c += __popcll(mask);
+    }
+    if (c == 0) return;
+    wave_sync();
+    for (int i = lane; i < c; i += 64) {
+        const Cand e = cand[i];
+        int r = 0;
+        for (int j = 0; j < c; ++j) r += beats(cand[j], e) ? 1 : 0;
+        srt[r] = e;
+    }
+    wave_sync();
+    Cand* list = p.lists + ((int64_t)m * p.nsplit + split) * p.k;
+    for (int j = lane; j < cnt; j += 64) {
+        const Cand e = list[j];
+        const int pos = j + count_beating(srt, c, e);
+        if (pos < p.k) mb[pos] = e;
+    }
+    for (int i = lane; i < c; i += 64) {
+        const Cand e = srt[i];
+        const int pos = i + count_beating(list, cnt, e);
+        if (pos < p.k) mb[pos] = e;
+    }
+    wave_sync();
+    const int ncnt = min(p.k, cnt + c);
+    for (int j = lane; j < ncnt; j += 64) list[j] = mb[j];
+    if (lane == 0) {
+        L.cnt[row] = ncnt;
+        // full list: a later score can only enter above the k-th (an equal score has a larger id: ids grow along the split)
+        if (ncnt == p.k) L.thr[row] = mb[p.k - 1].s;
+    }
+    wave_sync();
+}
+
+__global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    SearchLds& L = *reinterpret_cast<SearchLds*>(dsm);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
+    const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
+    const int m0 = tm * TM;
+    const int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
+    const int nk = p.d / BK;
+
+    if (tid < TM) {
+        const int m = m0 + tid;
+        // rows past M never pass the threshold test
+        L.thr[tid] = m < p.M ? -INFINITY : INFINITY;
+        L.bel[tid] = (m < p.M && p.below) ? p.below[m] : INFINITY;
+        L.cnt[tid] = 0;
+        L.flag[tid] = 0;
+    }
+    if (tid == 0) L.any = 0;
+    __syncthreads();
+
+    for (int t = t_begin; t < t_end; ++t) {
+        const int n0 = t * TN;
+        f32x4_t acc[4][4];   // [query block qb][document block db]
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        uint4 sq[4], sd[4];
+        stage(p, m0, n0, 0, tid, sq, sd);
+        commit(L.ops, L.ops + PANEL, tid, sq, sd);
+        __syncthreads();
+        for (int kc = 0; kc < nk; ++kc) {
+            const char* qb_ = L.ops + (kc & 1) * 2 * PANEL;
+            const char* db_ = qb_ + PANEL;
+            // the last chunk is staged twice (unconditional, so the staging registers never leave the register file)
+            stage(p, m0, n0, min(kc + 1, nk - 1) * BK, tid, sq, sd);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8_t fq[4], fd[4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    fq[b] = *reinterpret_cast<const bf16x8_t*>(qb_ + poff(wq * 64 + b * 16 + l15, ks * 4 + lh));
+                    fd[b] = *reinterpret_cast<const bf16x8_t*>(db_ + poff(wd * 64 + b * 16 + l15, ks * 4 + lh));
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[b], fq[a], acc[a][b], 0, 0, 0);
+            }
+            char* nq = L.ops + ((kc + 1) & 1) * 2 * PANEL;   // read last in chunk kc - 1, behind the barrier below
+            commit(nq, nq + PANEL, tid, sq, sd);
+            __syncthreads();
+        }
+
+        // acc[a][b][r] = score(query m0 + wq*64 + a*16 + l15, document n0 + wd*64 + b*16 + 4*lh + r)
+        bool hit = false;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int row = wq * 64 + a * 16 + l15;
+            const float thr = L.thr[row], bel = L.bel[row];
+            bool h = false;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = acc[a][b][r];
+                    h |= (v > thr) & (v < bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
+                }
+            if (h) L.flag[row] = 1;
+            hit |= h;
+        }
+        if (hit) L.any = 1;
+        __syncthreads();
+        if (L.any) {
+            float* tile = reinterpret_cast<float*>(L.ops);   // the operand buffers are free until the next tile
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    *reinterpret_cast<f32x4_t*>(tile + (wq * 64 + a * 16 + l15) * TN + wd * 64 + b * 16 + 4 * lh) = acc[a][b];
+            __syncthreads();
+            for (int row = wave; row < TM; row += 4)
+                if (L.flag[row]) insert_row(p, L, tile, row, m0 + row, n0, split, wave, lane);
+            __syncthreads();
+            if (tid < TM) L.flag[tid] = 0;
+            if (tid == 0) L.any = 0;
+        }
+        __syncthreads();
+    }
+    if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
+}
+
+// one wave per query row: merge the row's nsplit sorted lists into its top-k
+__global__ __launch_bounds__(256) void merge_splits_kernel(const Cand* __restrict__ lists, const int* __restrict__ counts,
+                                                           int M, int nsplit, int k, float* __restrict__ out_s,
+                                                           int64_t* __restrict__ out_id) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const Cand* base = lists + (int64_t)row * nsplit * k;
+    const int* cnt = counts + (int64_t)row * nsplit;
+    int total = 0;
+    for (int s = 0; s < nsplit; ++s) total += cnt[s];
+    for (int idx = lane; idx < nsplit * k; idx += 64) {
+        const int s = idx / k, j = idx - s * k;
+        if (j >= cnt[s]) continue;
+        const Cand e = base[(int64_t)s * k + j];
+        int rank = j;
+        for (int s2 = 0; s2 < nsplit && rank < k; ++s2)
+            if (s2 != s) rank += count_beating(base + (int64_t)s2 * k, cnt[s2], e);
+        if (rank < k) {
+            out_s[(int64_t)row * k + rank] = e.s;
+            out_id[(int64_t)row * k + rank] = e.id;
+        }
+    }
+    for (int r = min(total, k) + lane; r < k; r += 64) {
+        out_s[(int64_t)row * k + r] = -INFINITY;
+        out_id[(int64_t)row * k + r] = -1;
+    }
+}
+
+int auto_splits(int M, long N, int nsplit) {
+    const int tiles_m = (M + TM - 1) / TM;
+    const long tiles_n = (N + TN - 1) / TN;
+    if (nsplit <= 0) nsplit = (SPLIT_TARGET_WG + tiles_m - 1) / tiles_m;
+    nsplit = min(nsplit, MAXSPLIT);
+    return (int)max(1L, min((long)nsplit, tiles_n));
+}
+
+}  // namespace
+
+extern "C" {
+
+long cx_search_ws_bytes(int M, long N, int k, int nsplit) {
+    if (M <= 0 || N <= 0 || k <= 0) return 0;
+    const long s = auto_splits(M, N, nsplit);
+    return (long)M * s * ((long)k * (long)sizeof(Cand) + (long)sizeof(int)) + 16;
+}
+
+int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
+                   const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, int nsplit, void* ws,
+                   float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Q || !out_scores || !out_ids || (N > 0 && (!D || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
+    if (ldq < d || (ldq % 8) != 0 || (N > 0 && (ldd < d || (ldd % 8) != 0))) return CX_ERR_ALIGN;
+    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
+    Cand* lists = reinterpret_cast<Cand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
+    if (N > 0) {
+        SearchParams p = {};
+        p.Q = Q; p.D = D; p.ldq = ldq; p.ldd = ldd;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = ns;
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
+        p.lists = lists; p.counts = counts;
+        const int tiles_m = (M + TM - 1) / TM;
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel), (int)sizeof(SearchLds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(SearchLds), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    // N == 0: counts stays null and every row is padding
+    hipLaunchKernelGGL(merge_splits_kernel, dim3((M + 3) / 4), dim3(256), 0, s, lists, counts, M, N > 0 ? ns : 0, k,
+                       out_scores, out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+}  // extern "C"

@@ -330,6 +330,20 @@ int cx_infonce_fwd(const float* Q, const float* D, const int64_t* labels, float 
 long cx_infonce_argmax_ws_floats(int N, int G);
 int cx_infonce_fwd_argmax(const float* Q, const float* D, const int64_t* labels, float scale, float* ws, float* lse,
                           float* loss_rows, int32_t* argmax, int N, int G, int dim, int ldq, int ldd, void* stream);
+/* ---- exact inner-product top-k search (faiss IndexFlatIP.search; scripts/text/index_filtering.py:363-391,
+ *          scripts/text/get_negatives.py:111-196, scripts/text/mine_beir_negatives_full.py:98-136) ----------------------
+ * Q:(M,d) ldq and D:(N,d) ldd bf16 row-major, d % 64 == 0, 64 <= d <= 1024, N <= 2^31 - 129 rows (byte offsets are 64-bit).
+ * Per query row: the k (1 <= k <= 1024) largest scores s = q . d^T (fp32 accumulation) and their corpus ids, in descending
+ * score order with ties to the lower id; rows with fewer than k admissible documents are padded with (-inf, -1).
+ * out_scores:(M,k) fp32, out_ids:(M,k) int64.  Optional per-row filters: excl_ptr:(M+1) / excl_ids int64 = CSR lists of ids
+ * the row must not return (absolute offsets into excl_ids), below:(M) fp32 = exclusive upper bound on the score.
+ * nsplit = number of corpus ranges searched in parallel (<= 0: chosen from M and N); the result does not depend on it.
+ * ws: 16-B aligned scratch of cx_search_ws_bytes(M, N, k, nsplit) bytes (same nsplit), need not be initialised.
+ * The (M,N) scores are never written; deterministic, no atomics.  Q, D 16-B aligned and ldq / ldd % 8 == 0 (CX_ERR_ALIGN). */
+long cx_search_ws_bytes(int M, long N, int k, int nsplit);
+int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
+                   const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, int nsplit, void* ws,
+                   float* out_scores, int64_t* out_ids, void* stream);
 /* backward of  coef * sum_i loss_rows[i]:  Gm[i][j] = coef*scale*(softmax_ij - [j==label_i]) is written to
  * Gmat:(N,G) and GmatT:(G,N) fp32 scratch; dQ:(N,dim) = Gm D, dD:(G,dim) = Gm^T Q (overwritten);
  * dscale_accum (may be NULL): += coef * sum_ij (softmax_ij - y_ij) * (Q D^T)_ij   (d loss / d scale).
