@@ -42,7 +42,7 @@ CX_DEVICE uint16_t elem16(const uint4& v, int e) {
 }
 
 // Load chunks cp and cp+4 (8 bf16 each) of one 64-wide head row and apply the non-interleaved rotation at
-// position `pos` (fp32 math, one bf16 rounding -- same as the reference op).
+// position `pos` (fp32 math in rotary_pair's fixed operation order, one bf16 rounding).
 CX_DEVICE void load_row_pair(const bf16_t* row, int cp, const float* cosv, const float* sinv, int pos, uint4& lo,
                              uint4& hi) {
     lo = *reinterpret_cast<const uint4*>(row + cp * 8);
@@ -55,8 +55,7 @@ CX_DEVICE void load_row_pair(const bf16_t* row, int cp, const float* cosv, const
         const float* s = sinv + (size_t)pos * 32 + cp * 8;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            o1[e] = x1[e] * c[e] - x2[e] * s[e];
-            o2[e] = x2[e] * c[e] + x1[e] * s[e];
+            rotary_pair(x1[e], x2[e], c[e], s[e], o1[e], o2[e]);
         }
         lo = pack8(o1);
         hi = pack8(o2);
@@ -73,8 +72,7 @@ CX_DEVICE void rotate_loaded(uint4& lo, uint4& hi, int cp, const float* cosv, co
     const float* s = sinv + (size_t)pos * 32 + cp * 8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        o1[e] = x1[e] * c[e] - x2[e] * s[e];
-        o2[e] = x2[e] * c[e] + x1[e] * s[e];
+        rotary_pair(x1[e], x2[e], c[e], s[e], o1[e], o2[e]);
     }
     lo = pack8(o1);
     hi = pack8(o2);
@@ -386,8 +384,7 @@ CX_DEVICE void rot8(const uint4& lo_in, const uint4& hi_in, const float4 (&c)[2]
     const float ss[8] = {s[0].x, s[0].y, s[0].z, s[0].w, s[1].x, s[1].y, s[1].z, s[1].w};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        o1[e] = x1[e] * cc[e] - x2[e] * ss[e];
-        o2[e] = x2[e] * cc[e] + x1[e] * ss[e];
+        rotary_pair(x1[e], x2[e], cc[e], ss[e], o1[e], o2[e]);
     }
     lo = pack8(o1);
     hi = pack8(o2);

@@ -35,6 +35,19 @@ CX_DEVICE uint32_t pack_bf16x2(float lo, float hi) {
 }
 CX_DEVICE bf16_t f32_to_bf16(float f) { return (bf16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }
 
+// The rotary rotation of one (x1, x2) pair in ONE fixed fp32 operation order: the second product is rounded by itself, the
+// first is fused into the sum (a v_mul_f32 and a v_fma_f32 per result: the instruction count of the contracted form, no time
+// lost in scripts/attn_microbench.py).  Every kernel that rotates q / k goes through here, because the result is rounded to bf16 next and a value
+// that sits on a bf16 tie goes up or down with the last fp32 bit: left to `-ffp-contract`, the fused S <= 128 backward fused
+// the other product than the forward kernels did, rotated such a q element to the neighbouring bf16 value and recomputed
+// P = exp(s - lse) against an lse formed from a different q -- a whole P row off by exp(ulp_bf16(q) * k * scale), 1.9 % on
+// inputs with |q| ~ 6 (tests/test_attention_edges_gpu.py, family shift_neg).  tests/attn_ref.py performs the same operations.
+CX_DEVICE void rotary_pair(float x1, float x2, float c, float s, float& o1, float& o2) {
+#pragma clang fp contract(off)
+    o1 = __builtin_fmaf(x1, c, -(x2 * s));
+    o2 = __builtin_fmaf(x2, c, x1 * s);
+}
+
 // Backward of act = y * silu(g) from the saved (act, gate) pair (round 3's compact save: y = act / silu(g) is recovered
 // inside the derivative):  d y = d * g * s,  d gate = d * y * silu'(g) = d * act * (1 / g + 1 - s),  s = sigmoid(g).
 // An exactly-zero gate (or a silu that underflowed) means act = 0, y is not recoverable and d gate comes out 0.  1 / g is

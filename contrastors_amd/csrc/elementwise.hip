@@ -438,8 +438,7 @@ __global__ __launch_bounds__(256) void rotary_kernel(bf16_t* __restrict__ x, lon
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float c = cosv[pos * 32 + ch * 8 + e], sn = sign * sinv[pos * 32 + ch * 8 + e];
-            o1[e] = x1[e] * c - x2[e] * sn;
-            o2[e] = x2[e] * c + x1[e] * sn;
+            rotary_pair(x1[e], x2[e], c, sn, o1[e], o2[e]);   // (bit-identical to the attention kernels' rotate-on-load)
         }
         *reinterpret_cast<uint4*>(base + ch * 8) = pack8(o1);
         *reinterpret_cast<uint4*>(base + 32 + ch * 8) = pack8(o2);
