@@ -6,6 +6,10 @@
 the (queries x corpus) scores.  `search` adds what the margin miner needs on top of faiss: per-row excluded ids (the
 positives) and a per-row exclusive score bound (margin * s(q, pos)).
 
+`BinaryFlatIndex` is the same surface over sign codes (faiss `IndexBinaryFlat`, d / 8 bytes per vector) for the recipes
+trained with `hamming: true`; `rescore` / `search_binary_rescored` re-score its candidates exactly against the bf16 rows,
+which may stay on the host or in a memory-mapped file (csrc/search_binary.hip).
+
 `encode` is the embedding side: this project's BiEncoder under no_grad, length-sorted batches, results in input order.
 """
 from __future__ import annotations
@@ -29,8 +33,8 @@ def _to_device_2d(x, d: int, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.bfloat16).contiguous()
 
 
-def _exclusion_csr(exclude, M: int, device) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """exclude: None, a length-M sequence of id lists, or a (row_ptr (M+1), ids) pair -> int64 device CSR."""
+def _exclusion_csr_host(exclude, M: int) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """exclude: None, a length-M sequence of id lists, or a (row_ptr (M+1), ids) pair -> int64 host CSR (validated)."""
     if exclude is None:
         return None, None
     if isinstance(exclude, tuple) and len(exclude) == 2 and not isinstance(exclude[0], (list, tuple)):
@@ -46,6 +50,14 @@ def _exclusion_csr(exclude, M: int, device) -> Tuple[Optional[torch.Tensor], Opt
     if row_ptr.numel() != M + 1 or int(row_ptr[0]) != 0 or bool((row_ptr[1:] < row_ptr[:-1]).any()) \
             or int(row_ptr[-1]) != ids.numel():
         raise ValueError("exclude: malformed CSR (row_ptr must be M+1 non-decreasing offsets from 0 to len(ids))")
+    return row_ptr, ids
+
+
+def _exclusion_csr(exclude, M: int, device) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """exclude: None, a length-M sequence of id lists, or a (row_ptr (M+1), ids) pair -> int64 device CSR."""
+    row_ptr, ids = _exclusion_csr_host(exclude, M)
+    if row_ptr is None:
+        return None, None
     if ids.numel() == 0:
         ids = torch.zeros(1, dtype=torch.int64)   # a valid pointer; no row reads it
     return row_ptr.to(device), ids.to(device)
@@ -148,6 +160,278 @@ class FlatIPIndex:
         if as_numpy:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
+
+
+MAX_CANDIDATES = 4096             # cx_rescore_topk's candidate-list bound
+
+
+def _check_code_dim(d: int) -> None:
+    if d % 64 or not 64 <= d <= 1024:
+        raise ValueError(f"d must be a multiple of 64 in [64, 1024], got {d}")
+
+
+def pack_sign_bits(x):
+    """Sign codes of the rows of x (n, d): uint8 (n, d / 8) in the layout of numpy.packbits(x > 0, axis=1) -- dimension 0 is
+    bit 7 of byte 0; +-0 and NaN give bit 0 -- which is what faiss binary indexes and sentence-transformers "ubinary" take.
+    A tensor on the GPU goes through cx_pack_sign_bits (fp32 and bf16 as they are, other dtypes as fp32; a row stride is
+    honoured); a CPU tensor or a numpy array through numpy.  Same bytes either way; torch in -> torch out."""
+    is_torch = isinstance(x, torch.Tensor)
+    if not is_torch:
+        x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError(f"expected a (n, d) array, got shape {tuple(x.shape)}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    _check_code_dim(d)
+    if not is_torch or x.device.type != "cuda":
+        a = x.float().numpy() if is_torch else x
+        out = np.packbits(a > 0, axis=1)
+        return torch.from_numpy(out) if is_torch else out
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    if x.stride(1) != 1 or (n > 1 and x.stride(0) < d):
+        x = x.contiguous()
+    out = torch.empty(n, d // 8, dtype=torch.uint8, device=x.device)
+    if n:
+        with torch.cuda.device(x.device):
+            _C.check(_C.lib().cx_pack_sign_bits(x.data_ptr(), 0 if x.dtype == torch.float32 else 1, n, d,
+                                                x.stride(0) if n > 1 else d, out.data_ptr(), d // 8, _C.cur_stream()),
+                     "cx_pack_sign_bits")
+    return out
+
+
+class BinaryFlatIndex:
+    """Exact Hamming index over sign codes on one GPU (faiss IndexBinaryFlat; d counts BITS): d / 8 bytes per vector where
+    FlatIPIndex keeps 2 d.  Same surface as FlatIPIndex; distances come from cx_search_hamming_topk (csrc/search_binary.hip)."""
+
+    def __init__(self, d: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        _check_code_dim(d)
+        self.d = int(d)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("BinaryFlatIndex runs on the GPU (cx_search_hamming_topk); there is no CPU path")
+        self.workspace_bytes = int(workspace_bytes)
+        self._store: Optional[torch.Tensor] = None   # (capacity, d / 8) uint8; rows [0, ntotal) are the corpus
+        self.ntotal = 0
+
+    def reset(self) -> None:
+        self._store = None
+        self.ntotal = 0
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """The stored codes, (ntotal, d / 8) uint8 (a view)."""
+        if self._store is None:
+            return torch.empty(0, self.d // 8, dtype=torch.uint8, device=self.device)
+        return self._store[: self.ntotal]
+
+    def reserve(self, n: int) -> None:
+        """Allocate room for n codes in total, so that adding a corpus in chunks never copies it."""
+        if n > MAX_NTOTAL:
+            raise ValueError(f"BinaryFlatIndex holds at most {MAX_NTOTAL} vectors")
+        cap = 0 if self._store is None else self._store.shape[0]
+        if n > cap:
+            grown = torch.empty(n, self.d // 8, dtype=torch.uint8, device=self.device)
+            if self.ntotal:
+                grown[: self.ntotal].copy_(self._store[: self.ntotal])
+            self._store = grown
+
+    def _codes_of(self, x) -> torch.Tensor:
+        """(n, d) float rows (binarised by sign) or (n, d / 8) uint8 codes -> codes on the index's device."""
+        t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        if t.dim() != 2:
+            raise ValueError(f"expected a 2-d array, got shape {tuple(t.shape)}")
+        if t.dtype == torch.uint8:
+            if t.shape[1] != self.d // 8:
+                raise ValueError(f"expected (n, {self.d // 8}) uint8 codes, got shape {tuple(t.shape)}")
+            return t.to(self.device).contiguous()
+        if t.shape[1] != self.d:
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(t.shape)}")
+        return pack_sign_bits(t.to(self.device))
+
+    def add(self, x) -> None:
+        """Append rows: float vectors are binarised by sign (x > 0), uint8 (n, d / 8) arrays are taken as codes."""
+        c = self._codes_of(x)
+        n = c.shape[0]
+        self.reserve(self.ntotal + n)
+        self._store[self.ntotal: self.ntotal + n].copy_(c)
+        self.ntotal += n
+
+    def batch_rows(self, M: int, k: int) -> int:
+        h = _C.lib()
+        m = M
+        while m > 128 and h.cx_search_hamming_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
+            m = max(128, (m // 2) // 128 * 128)
+        return m
+
+    def search(self, queries, k: int, exclude=None, max_dist=None, nsplit: int = 0):
+        """-> (dist (M, k) int32, ids (M, k) int64): per query the k nearest stored codes by Hamming distance, ascending, ties
+        to the lower id; missing entries are (INT32_MAX, -1).  queries: float rows or uint8 codes, as for add.  exclude: as
+        FlatIPIndex.search; max_dist: per-row INCLUSIVE upper bound on the distance.  numpy in -> numpy out, torch in -> torch
+        out on the index's device.  nsplit has no effect on the result."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        M = int(np.shape(queries)[0])
+        xptr, xids = _exclusion_csr_host(exclude, M)
+        q = self._codes_of(queries)
+        if xptr is not None:
+            xptr = xptr.to(self.device)
+            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
+        md = None
+        if max_dist is not None:
+            md = torch.as_tensor(np.asarray(max_dist) if not isinstance(max_dist, torch.Tensor) else max_dist)
+            md = md.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            if md.numel() != M:
+                raise ValueError(f"max_dist has {md.numel()} entries for {M} queries")
+        dist = torch.empty(M, k, dtype=torch.int32, device=self.device)
+        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
+        if M:
+            h = _C.lib()
+            nb = self.d // 8
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                mb = self.batch_rows(M, k)
+                ws = None
+                if self.ntotal:
+                    last = M - (M - 1) // mb * mb
+                    nbytes = max(h.cx_search_hamming_ws_bytes(mb, self.ntotal, k, nsplit),
+                                 h.cx_search_hamming_ws_bytes(last, self.ntotal, k, nsplit))
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                D = self.codes
+                for b0 in range(0, M, mb):
+                    m = min(mb, M - b0)
+                    _C.check(h.cx_search_hamming_topk(q[b0].data_ptr(), D.data_ptr() if self.ntotal else None, m,
+                                                      self.ntotal, self.d, nb, nb, k,
+                                                      None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
+                                                      None if md is None else md[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
+                                                      dist[b0].data_ptr(), ids[b0].data_ptr(), stream),
+                             "cx_search_hamming_topk")
+        if as_numpy:
+            return dist.cpu().numpy(), ids.cpu().numpy()
+        return dist, ids
+
+
+RESCORE_UPLOAD_BYTES = 1 << 30   # host sources: bf16 bytes of gathered rows uploaded per query batch, at most
+
+
+def _rescore_call(q, D, cand, ids, k, bel, scores, out_ids):
+    M, c = cand.shape
+    _C.check(_C.lib().cx_rescore_topk(q.data_ptr(), D.data_ptr() if D.shape[0] else None, cand.data_ptr(), _C.ptr(ids), M,
+                                      D.shape[0], q.shape[1], q.stride(0), D.stride(0) if D.shape[0] else q.shape[1], c, k,
+                                      _C.ptr(bel), scores.data_ptr(), out_ids.data_ptr(), _C.cur_stream()), "cx_rescore_topk")
+
+
+def rescore(queries, cand_ids, vectors, k: int, below=None, device=None):
+    """Exact re-scoring of per-query candidate lists (the second stage of a binary search).
+
+    queries (M, d); cand_ids (M, c) int64 corpus ids, -1 = no candidate, distinct within a row, c <= 4096; vectors: the
+    full-precision corpus, (R, d) -- a bf16 tensor on the GPU, or a CPU tensor / numpy array / numpy memmap (rounded to bf16
+    as FlatIPIndex.add rounds).  For a host source the distinct candidate rows of a query batch are gathered on the host,
+    uploaded once and the ids remapped, so only candidates ever cross the bus.  -> (scores (M, k) float32, ids (M, k) int64):
+    the k best candidates by (score descending, id ascending) with CORPUS ids, (-inf, -1) where there are fewer; below: per-row
+    exclusive upper bound on the score.  A pair's score has the bits FlatIPIndex.search gives it.  numpy queries -> numpy
+    out.  device: the GPU that scores host rows (default: the queries' GPU, else the current one)."""
+    as_numpy = not isinstance(queries, torch.Tensor)
+    k = int(k)
+    on_device = isinstance(vectors, torch.Tensor) and vectors.device.type == "cuda"
+    if on_device:
+        dev = vectors.device
+    elif device is not None:
+        dev = torch.device(device)
+    else:   # host rows: score where the queries are, else on the current GPU
+        dev = queries.device if not as_numpy and queries.is_cuda else torch.device("cuda")
+    if len(np.shape(vectors)) != 2:
+        raise ValueError(f"vectors must be (R, d), got shape {tuple(np.shape(vectors))}")
+    R, d = int(np.shape(vectors)[0]), int(np.shape(vectors)[1])
+    _check_code_dim(d)
+    cand = torch.as_tensor(cand_ids if isinstance(cand_ids, torch.Tensor) else np.asarray(cand_ids)).to(torch.int64)
+    if cand.dim() != 2:
+        raise ValueError(f"cand_ids must be (M, c), got shape {tuple(cand.shape)}")
+    M, c = cand.shape
+    if not 1 <= c <= MAX_CANDIDATES:
+        raise ValueError(f"the candidate lists must hold 1 to {MAX_CANDIDATES} ids, got {c}")
+    if not 1 <= k <= min(c, MAX_K):
+        raise ValueError(f"k must be in [1, min(c, {MAX_K})] = [1, {min(c, MAX_K)}], got {k}")
+    if np.shape(queries)[0] != M:
+        raise ValueError(f"{np.shape(queries)[0]} queries for {M} candidate lists")
+    q = _to_device_2d(queries, d, dev)
+    bel = None
+    if below is not None:
+        bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
+        bel = bel.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if bel.numel() != M:
+            raise ValueError(f"below has {bel.numel()} entries for {M} queries")
+    scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+    ids = torch.empty(M, k, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        if on_device:
+            D = vectors if vectors.dtype == torch.bfloat16 else vectors.to(torch.bfloat16)
+            if D.stride(1) != 1 or D.stride(0) % 8 or D.data_ptr() % 16:
+                D = D.contiguous()
+            if M:
+                _rescore_call(q, D, cand.to(dev).contiguous(), None, k, bel, scores, ids)
+        else:
+            host = cand.cpu().numpy()
+            mb = max(1, RESCORE_UPLOAD_BYTES // (c * d * 2))
+            for b0 in range(0, M, mb):
+                hb = host[b0: b0 + mb]
+                uniq = np.unique(hb[(hb >= 0) & (hb < R)])
+                rows = vectors[torch.from_numpy(uniq)] if isinstance(vectors, torch.Tensor) else \
+                    torch.from_numpy(np.ascontiguousarray(vectors[uniq]))
+                D = rows.to(device=dev, dtype=torch.bfloat16).contiguous()
+                local = np.searchsorted(uniq, hb) if uniq.size else np.zeros_like(hb)
+                local = np.where((hb >= 0) & (hb < R), local, -1).astype(np.int64)
+                _rescore_call(q[b0: b0 + mb], D, torch.from_numpy(local).to(dev), torch.from_numpy(hb).to(dev).contiguous(),
+                              k, None if bel is None else bel[b0: b0 + mb], scores[b0: b0 + mb], ids[b0: b0 + mb])
+    if as_numpy:
+        return scores.cpu().numpy(), ids.cpu().numpy()
+    return scores, ids
+
+
+def search_binary_rescored(index: BinaryFlatIndex, vectors, queries, k: int, rescore_factor: int = 4, exclude=None,
+                           below=None):
+    """Coarse Hamming search + exact re-scoring: the min(k * rescore_factor, 4096) nearest codes of `index` per query, then
+    the k best of those by exact inner product with `vectors` (the corpus the codes were made from: see rescore).  exclude
+    applies to the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it when the
+    candidate lists cover the corpus.  Lists longer than the Hamming kernel's k bound (1024) are fetched in pages of 1024,
+    each page excluding the ones before it (the order is strict, so the pages are the consecutive runs of one ranking)."""
+    k = int(k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+    if int(rescore_factor) < 1:
+        raise ValueError(f"rescore_factor must be at least 1, got {rescore_factor}")
+    if np.shape(vectors)[0] != index.ntotal:
+        raise ValueError(f"{np.shape(vectors)[0]} vectors for an index of {index.ntotal} codes")
+    as_numpy = not isinstance(queries, torch.Tensor)
+    c = max(k, min(k * int(rescore_factor), MAX_CANDIDATES))
+    M = int(np.shape(queries)[0])
+    qd = _to_device_2d(queries, index.d, index.device)
+    qc = pack_sign_bits(qd)
+    xptr, xids = _exclusion_csr_host(exclude, M)
+    pages = []
+    for p0 in range(0, c, MAX_K):
+        kp = min(MAX_K, c - p0)
+        ex = None if xptr is None else (xptr, xids)
+        if pages:
+            # CSR of (the caller's exclusions + the pages so far) per row
+            prev = torch.cat(pages, 1).cpu()
+            base = [xids[int(xptr[r]): int(xptr[r + 1])] for r in range(M)] if xptr is not None else [prev[:0, 0]] * M
+            rows = [torch.cat([base[r], prev[r][prev[r] >= 0]]) for r in range(M)]
+            ptr = torch.zeros(M + 1, dtype=torch.int64)
+            ptr[1:] = torch.cumsum(torch.as_tensor([len(r) for r in rows], dtype=torch.int64), 0)
+            ex = (ptr.numpy(), (torch.cat(rows) if rows else prev[:0, 0]).numpy())
+        pages.append(index.search(qc, kp, exclude=ex)[1])
+        if index.ntotal <= p0 + kp:
+            break
+    cand = torch.cat(pages, 1) if len(pages) > 1 else pages[0]
+    s, i = rescore(qd, cand, vectors, min(k, cand.shape[1]), below=below, device=index.device)
+    if s.shape[1] < k:    # fewer candidates than k: an index smaller than k
+        s = torch.cat([s, torch.full((M, k - s.shape[1]), -float("inf"), dtype=s.dtype, device=s.device)], 1)
+        i = torch.cat([i, torch.full((M, k - i.shape[1]), -1, dtype=i.dtype, device=i.device)], 1)
+    if as_numpy:
+        return s.cpu().numpy(), i.cpu().numpy()
+    return s, i
 
 
 def encode(model, texts: Sequence[str], tokenizer, batch_size: int = 256, max_length: int = 512,

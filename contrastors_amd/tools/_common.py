@@ -30,8 +30,9 @@ def write_shards(records: List[dict], output_dir, metadata: dict, shard_size: in
     return paths
 
 
-def load_npy(path, n: int, what: str) -> np.ndarray:
-    x = np.load(path)
+def load_npy(path, n: int, what: str, mmap: bool = False) -> np.ndarray:
+    """mmap: map the file instead of reading it (the binary coarse search only ever gathers candidate rows from it)."""
+    x = np.load(path, mmap_mode="r" if mmap else None)
     if x.ndim != 2 or x.shape[0] != n:
         raise SystemExit(f"error: {what} embeddings {path} have shape {x.shape}, expected ({n}, d)")
     return x
@@ -59,12 +60,38 @@ def encode_texts(texts: List[str], checkpoint: Optional[str], tokenizer_path: Op
     return encode(model, [prefix + t for t in texts], tok, batch_size=batch_size, max_length=max_length)
 
 
-def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None):
-    """-> (scores, ids) numpy: exact inner-product top-k over the bf16 corpus (FlatIPIndex)."""
+COARSE = ("exact", "binary")
+ADD_ROWS = 1 << 18   # binary: document rows binarised per upload
+
+
+def add_search_arguments(ap) -> None:
+    ap.add_argument("--coarse", choices=COARSE, default="exact",
+                    help="exact: bf16 inner-product search of the whole corpus on the device; binary: Hamming search over "
+                         "sign codes (1/16 of the memory), then exact re-scoring of k * rescore_factor candidates against "
+                         "the memory-mapped document .npy")
+    ap.add_argument("--rescore_factor", type=int, default=4,
+                    help="binary: candidates re-scored per returned neighbour (k * rescore_factor, at most 4096)")
+
+
+def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, coarse: str = "exact",
+           rescore_factor: int = 4):
+    """-> (scores, ids) numpy.  coarse="exact": exact inner-product top-k over the bf16 corpus (FlatIPIndex).
+    coarse="binary": Hamming top-(k * rescore_factor) over sign codes (BinaryFlatIndex), re-scored exactly against doc_emb,
+    which stays on the host (an array or a memmap); equal to "exact" once the candidates cover the corpus."""
     import torch
 
-    from ..search import FlatIPIndex
+    from ..search import BinaryFlatIndex, FlatIPIndex, search_binary_rescored
 
+    if coarse not in COARSE:
+        raise ValueError(f"coarse must be one of {COARSE}, got {coarse!r}")
+    if coarse == "binary":
+        n, d = np.shape(doc_emb)
+        index = BinaryFlatIndex(d, device=device)
+        index.reserve(n)
+        for r0 in range(0, n, ADD_ROWS):
+            index.add(torch.as_tensor(np.asarray(doc_emb[r0: r0 + ADD_ROWS], dtype=np.float32)))
+        return search_binary_rescored(index, doc_emb, np.asarray(query_emb, dtype=np.float32), k, rescore_factor,
+                                      exclude=exclude, below=below)
     index = FlatIPIndex(np.shape(doc_emb)[1], device=device)
     index.add(torch.as_tensor(np.asarray(doc_emb, dtype=np.float32)))
     return index.search(np.asarray(query_emb, dtype=np.float32), k, exclude=exclude, below=below)

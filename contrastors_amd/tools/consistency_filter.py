@@ -18,7 +18,7 @@ from typing import List
 
 import numpy as np
 
-from ._common import encode_texts, load_npy, search
+from ._common import add_search_arguments, encode_texts, load_npy, search
 
 
 def keep_ids(ids: List, top_k_indices) -> List:
@@ -30,10 +30,11 @@ def keep_ids(ids: List, top_k_indices) -> List:
     return [order[j] for j in range(len(order)) if valid[j]]
 
 
-def filter_pairs(ids: List, q_emb, d_emb, device: str = "cuda", k: int = 2) -> List:
+def filter_pairs(ids: List, q_emb, d_emb, device: str = "cuda", k: int = 2, coarse: str = "exact",
+                 rescore_factor: int = 4) -> List:
     """ids[i] names pair i; -> the kept ids, in ascending id order."""
     pos = sorted(range(len(ids)), key=lambda i: ids[i])
-    _, top = search(np.asarray(d_emb)[pos], np.asarray(q_emb)[pos], k, device)
+    _, top = search(np.asarray(d_emb)[pos], np.asarray(q_emb)[pos], k, device, coarse=coarse, rescore_factor=rescore_factor)
     return keep_ids(ids, top)
 
 
@@ -64,6 +65,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--batch_size", type=int, default=256)
     ap.add_argument("--max_length", type=int, default=512)
     ap.add_argument("--device", default="cuda")
+    add_search_arguments(ap)
     return ap
 
 
@@ -77,7 +79,7 @@ def main(argv=None) -> int:
     if args.query_embeddings:
         q = np.load(args.query_embeddings)
         n = q.shape[0]
-        d = load_npy(args.document_embeddings, n, "document")
+        d = load_npy(args.document_embeddings, n, "document", mmap=args.coarse == "binary")
         ids = json.loads(Path(args.ids).read_text()) if args.ids else list(range(n))
         if len(ids) != n:
             ap.error(f"--ids has {len(ids)} entries for {n} pairs")
@@ -92,7 +94,7 @@ def main(argv=None) -> int:
                          args.max_length, args.device).cpu().numpy()
     if len(set(ids)) != len(ids):
         ap.error("pair ids must be unique")
-    kept = filter_pairs(ids, q, d, args.device, args.k)
+    kept = filter_pairs(ids, q, d, args.device, args.k, args.coarse, args.rescore_factor)
     out = Path(args.output_dir)
     out.mkdir(parents=True, exist_ok=True)
     n_existing = len(list(out.glob("ids_to_keep_*.json")))

@@ -37,7 +37,7 @@ from typing import Dict, List
 
 import numpy as np
 
-from ._common import encode_texts, load_npy, search, triplet_metadata, write_shards
+from ._common import add_search_arguments, encode_texts, load_npy, search, triplet_metadata, write_shards
 
 DEVIATIONS = """deviations from the reference scripts:
   the random fill (topk) and the record shuffle (margin) are seeded by --seed;
@@ -199,6 +199,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max_length", type=int, default=512)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
+    add_search_arguments(ap)
     return ap
 
 
@@ -207,7 +208,7 @@ def _embeddings(args, q_texts, d_texts):
         raise SystemExit("error: give both --query_embeddings and --document_embeddings, or neither")
     if args.query_embeddings:
         return (load_npy(args.query_embeddings, len(q_texts), "query"),
-                load_npy(args.document_embeddings, len(d_texts), "document"))
+                load_npy(args.document_embeddings, len(d_texts), "document", mmap=args.coarse == "binary"))
     q = encode_texts(q_texts, args.model, args.tokenizer, args.batch_size, args.max_length, args.device, args.query_prefix)
     d = encode_texts(d_texts, args.model, args.tokenizer, args.batch_size, args.max_length, args.device,
                      args.document_prefix)
@@ -240,7 +241,7 @@ def main(argv=None) -> int:
     if topk:
         queries, documents, records = load_records(args.dataset, args.query_key, args.document_key, args.negatives_key)
         q_emb, d_emb = _embeddings(args, queries, documents)
-        _, indices = search(d_emb, q_emb, args.k, args.device)
+        _, indices = search(d_emb, q_emb, args.k, args.device, coarse=args.coarse, rescore_factor=args.rescore_factor)
         records = select_topk(records, documents, indices, args.k, args.query_key, args.document_key,
                               args.negatives_key, np.random.RandomState(args.seed))
         write_shards(records, args.output_dir, meta)
@@ -257,11 +258,12 @@ def main(argv=None) -> int:
         if missing:
             ap.error(f"--query_ids lacks {len(missing)} queries of the qrels split, e.g. {missing[0]!r}")
         q_emb = q_all[[where[qid] for qid in queries]]
-        d_emb = load_npy(args.document_embeddings, len(documents), "document")
+        d_emb = load_npy(args.document_embeddings, len(documents), "document", mmap=args.coarse == "binary")
     else:
         q_emb, d_emb = _embeddings(args, list(queries.values()), documents)
     pairs, rows, excl, below = margin_pairs(qrels, qid2index, docid2index, q_emb, d_emb, args.margin)
-    _, indices = search(d_emb, np.asarray(q_emb)[rows], args.max_negatives, args.device, exclude=excl, below=below)
+    _, indices = search(d_emb, np.asarray(q_emb)[rows], args.max_negatives, args.device, exclude=excl, below=below,
+                        coarse=args.coarse, rescore_factor=args.rescore_factor)
     mined, dropped = select_margin(pairs, indices, corpus, queries, documents, args.k, args.query_key,
                                    args.document_key, args.negatives_key)
     random.Random(args.seed).shuffle(mined)

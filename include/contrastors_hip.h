@@ -344,6 +344,30 @@ long cx_search_ws_bytes(int M, long N, int k, int nsplit);
 int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
                    const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, int nsplit, void* ws,
                    float* out_scores, int64_t* out_ids, void* stream);
+/* ---- binary (sign-bit) index with exact re-scoring (faiss IndexBinaryFlat, sentence-transformers "ubinary"; the recipes
+ *          with `hamming: true`; csrc/search_binary.hip).  Additive: cx_abi_version stays 10. ---------------------------------
+ * Sign codes: out:(rows, d/8) bytes, leading dimension ldo BYTES, in the layout of numpy.packbits(x > 0, axis=1) (dimension 0
+ * = bit 7 of byte 0; +-0 and NaN give bit 0).  X:(rows,d) with leading dimension ldx ELEMENTS, dtype 0 = fp32, 1 = bf16.
+ * d % 64 == 0, 64 <= d <= 1024. */
+int cx_pack_sign_bits(const void* X, int dtype, long rows, int d, long ldx, uint8_t* out, long ldo, void* stream);
+/* Hamming top-k over packed codes, argument for argument cx_search_topk: Qc:(M,d/8) ldq and Dc:(N,d/8) ldd bytes (leading
+ * dimensions in BYTES, % 8 == 0, pointers 8-B aligned: CX_ERR_ALIGN), d = the number of BITS.  Per query row the k smallest
+ * distances in ascending order, ties to the lower id, padded with (INT32_MAX, -1): out_dist:(M,k) int32, out_ids:(M,k) int64.
+ * excl_ptr / excl_ids as there; max_dist:(M) int32 = INCLUSIVE upper bound on the distance (NULL = none).  The result does
+ * not depend on nsplit; ws: 16-B aligned, cx_search_hamming_ws_bytes(M, N, k, nsplit) bytes.  The distances come off the matrix
+ * cores (codes expanded to +-64 int8 in the kernel, v_mfma_i32_16x16x64_i8, exact); deterministic, no atomics. */
+long cx_search_hamming_ws_bytes(int M, long N, int k, int nsplit);
+int cx_search_hamming_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, int d, long ldq, long ldd, int k,
+                           const int64_t* excl_ptr, const int64_t* excl_ids, const int32_t* max_dist, int nsplit, void* ws,
+                           int32_t* out_dist, int64_t* out_ids, void* stream);
+/* Exact re-scoring of candidate lists: Q:(M,d) ldq bf16, D:(R,d) ldd bf16, cand:(M,c) int64 row indices into D (entries < 0
+ * or >= R are skipped), ids:(M,c) int64 = what to report for each candidate (NULL: the row index).  Per query the k best
+ * candidates by (score descending, id ascending), padded with (-inf, -1); below:(M) fp32 = exclusive upper bound on the score
+ * (NULL = none).  1 <= c <= 4096, 1 <= k <= min(c, 1024).  The score of a pair has the bits cx_search_topk gives that pair
+ * (same instruction, same K order), so coarse search + re-scoring of every candidate equals the exact search. */
+int cx_rescore_topk(const uint16_t* Q, const uint16_t* D, const int64_t* cand, const int64_t* ids, int M, long R, int d,
+                    long ldq, long ldd, int c, int k, const float* below, float* out_scores, int64_t* out_ids,
+                    void* stream);
 /* backward of  coef * sum_i loss_rows[i]:  Gm[i][j] = coef*scale*(softmax_ij - [j==label_i]) is written to
  * Gmat:(N,G) and GmatT:(G,N) fp32 scratch; dQ:(N,dim) = Gm D, dD:(G,dim) = Gm^T Q (overwritten);
  * dscale_accum (may be NULL): += coef * sum_ij (softmax_ij - y_ij) * (Q D^T)_ij   (d loss / d scale).
