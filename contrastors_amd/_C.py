@@ -188,6 +188,9 @@ _SIGS = {
     "cx_search_hamming_ws_bytes": (i64, [i32, i64, i32, i32]),
     "cx_search_hamming_topk": (i32, [vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "cx_rescore_topk": (i32, [vp, vp, vp, vp, i32, i64, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
+    "cx_simkl_ws_floats": (i64, [i32, i32]),
+    "cx_simkl_fwd": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cx_simkl_bwd": (i32, [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cx_infonce_fp8_ws_floats": (i64, [i32, i32]),
     "cx_infonce_fp8_fwd": (i32, [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "cx_infonce_fp8_bwd": (i32, [vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32,

@@ -61,6 +61,9 @@ class TrainArgs(BaseModel):
     # model_args.gradient_checkpointing is a memory knob sized for 80 GB parts: auto = the top blocks keep their activations
     # as far as the free HBM allows (bit-identical results, less re-forward) | n blocks | 0 = recompute every block
     checkpoint_keep_layers: Union[int, str, None] = "auto"
+    # model_type: distill (sc/config.py:46-47, 79-84; sc/trainers/distill.py:341-385)
+    distill_loss_fn: str = "mse"
+    distill_temperature: float = 1.0
 
     @model_validator(mode="after")
     def _checks(self):
@@ -69,6 +72,8 @@ class TrainArgs(BaseModel):
         _parse_chunk(self.gradcache_chunk, "train_args.gradcache_chunk")
         _parse_resident(self.gradcache_resident, "train_args.gradcache_resident")
         _parse_keep(self.checkpoint_keep_layers, "train_args.checkpoint_keep_layers")
+        if self.distill_loss_fn not in ("mse", "kd", "towers", "stella"):   # sc/config.py:79-84
+            raise ValueError(f"Loss function {self.distill_loss_fn} not found in loss function registry")
         if self.exchange not in (None, "auto", "rccl", "oneshot"):
             raise ValueError(f"train_args.exchange must be auto, rccl or oneshot, got {self.exchange!r}")
         if self.use_fp8 and self.matryoshka_dims is not None:
@@ -140,6 +145,10 @@ class ModelArgs(BaseModel):
     # keys of the reference schema this path does not serve: accepted at their inert defaults, refused otherwise (a recipe
     # that sets them must not train as if it had not)
     num_experts: int = 0
+    # model_type: distill (sc/config.py:190-191; sc/trainers/distill.py:116-269).  ffn_div is read by DistillTrainer, which refuses
+    # the one branch it cannot serve; the YAML keeps parsing (contrastive_finetune_distill.yaml carries ffn_div: 2)
+    distill_init_pretrained: bool = False
+    ffn_div: Optional[int] = None
 
     @model_validator(mode="after")
     def _model_type(self):

@@ -6,6 +6,8 @@
 // here buys parity with the fp32 oracle at the 1e-6 level instead of bf16-logit noise (quirk 5, Appendix A).
 // MFMA is issued as (A := document rows, B := query rows) so a lane owns ONE query row: the online
 // log-sum-exp over documents is lane-local.
+// The same tile loop (sgemm_tile) carries the distillation trainer's similarity-KL loss: two products per tile, the soft-maxes of
+// both and their KL divergence without either matrix (simkl_kernel, cx_simkl_fwd / cx_simkl_bwd).
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
 
@@ -57,18 +59,14 @@ CX_DEVICE void scommit(char* tile, int tid, const SRegs& regs) {
     *reinterpret_cast<float4*>(tile + stile_off((256 + tid) >> 2, tid & 3)) = regs.r1;
 }
 
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void sgemm_nt_kernel(SgemmParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[4 * STILE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
+// One 128 x 128 tile of A B^T over the whole K range into acc (zeroed here): double-buffered LDS ring of 4 tiles, register-staged
+// global loads.  Ends on a __syncthreads(), so a second call may reuse the ring at once (simkl_kernel runs two back to back).
+// Each accumulator sees its MFMAs in k order whatever surrounds the call: the result bits depend on (A, B, K) alone.
+CX_DEVICE void sgemm_tile(const float* __restrict__ A, int lda, int M, const float* __restrict__ B, int ldb, int N, int K,
+                          int m0, int n0, char* smem, int tid, f32x16_t (&acc)[2][2]) {
+    const int lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
     const int wm = wave >> 1, wn = wave & 1;
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int lid = xcd_remap(blockIdx.x, nwg);
-    const int tn = lid % p.tiles_n, tm = lid / p.tiles_n;
-    const int m0 = tm * SBM, n0 = tn * SBN;
-    const int nk = (p.K + SBK - 1) / SBK;
-
-    f32x16_t acc[2][2];  // [n-block a][m-block b]
+    const int nk = (K + SBK - 1) / SBK;
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -77,8 +75,8 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_kernel(SgemmParams p) {
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 
     SRegs ar = {}, br = {};
-    sstage(p.A, p.lda, m0, p.M, 0, p.K, tid, ar);
-    sstage(p.B, p.ldb, n0, p.N, 0, p.K, tid, br);
+    sstage(A, lda, m0, M, 0, K, tid, ar);
+    sstage(B, ldb, n0, N, 0, K, tid, br);
     scommit(smem, tid, ar);
     scommit(smem + STILE, tid, br);
     __syncthreads();
@@ -88,8 +86,8 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_kernel(SgemmParams p) {
         char* nxt = smem + ((it + 1) & 1) * 2 * STILE;
         const bool more = (it + 1) < nk;
         if (more) {
-            sstage(p.A, p.lda, m0, p.M, (it + 1) * SBK, p.K, tid, ar);
-            sstage(p.B, p.ldb, n0, p.N, (it + 1) * SBK, p.K, tid, br);
+            sstage(A, lda, m0, M, (it + 1) * SBK, K, tid, ar);
+            sstage(B, ldb, n0, N, (it + 1) * SBK, K, tid, br);
         }
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -117,6 +115,20 @@ __global__ __launch_bounds__(256, 2) void sgemm_nt_kernel(SgemmParams p) {
         }
         __syncthreads();
     }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void sgemm_nt_kernel(SgemmParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[4 * STILE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int nwg = p.tiles_m * p.tiles_n;
+    const int lid = xcd_remap(blockIdx.x, nwg);
+    const int tn = lid % p.tiles_n, tm = lid / p.tiles_n;
+    const int m0 = tm * SBM, n0 = tn * SBN;
+
+    f32x16_t acc[2][2];  // [n-block a][m-block b]
+    sgemm_tile(p.A, p.lda, p.M, p.B, p.ldb, p.N, p.K, m0, n0, smem, tid, acc);
 
     // acc[a][b][r] = sum_k A[m][k] B[n][k],  m = m0 + wm*64 + b*32 + l31,  n = n0 + wn*64 + a*32 + acc_row(r,hi)
     if constexpr (EPI == EPI_STORE) {
@@ -254,6 +266,159 @@ __global__ __launch_bounds__(256) void lse_combine_kernel(const float* __restric
     }
 }
 
+// ---- similarity-KL (distillation `kd` loss, sc/trainers/distill.py:347-355): KL(softmax_j t || softmax_j s) per query row for
+// t = c <Qt_i, Dt_j>, s = c <Qs_i, Ds_j>, without either (N x G) matrix.
+//   kl_i = sum_j p_ij (t_ij - s_ij) - lse_t_i + lse_s_i
+// Both products of a tile run sgemm_tile back to back over the same LDS ring; the teacher's result waits in registers (2 x 64
+// accumulators per lane).  128 accumulator + 16 staging + 16 fragment registers: __launch_bounds__(256, 2) leaves 256 per lane and
+// compiles to 185 (forward) / 181 (gradient) VGPRs with no scratch (-Rpass-analysis=kernel-resource-usage), so two blocks share
+// a CU as they do for sgemm_nt_kernel<EPI_GRAD> (177); (256, 1) would buy nothing the kernel uses.
+struct SimklParams {
+    const float* Qs; const float* Ds; const float* Qt; const float* Dt;
+    int N, G, dim_s, dim_t, ldqs, ldds, ldqt, lddt;
+    int tiles_m, tiles_n, nparts;
+    float c;                                     // 1 / temperature
+    float* pmt; float* plt; float* pat; float* pms; float* pls;   // SIMKL_FWD: (N, nparts) partials, maxima in log2 units
+    const float* lse_s; const float* lse_t; float coef; float* Gm; float* GmT;   // SIMKL_GRAD
+};
+enum SimklMode { SIMKL_FWD = 0, SIMKL_GRAD = 1 };
+
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void simkl_kernel(SimklParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[4 * STILE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hi = lane >> 5, l31 = lane & 31;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int nwg = p.tiles_m * p.tiles_n;
+    const int lid = xcd_remap(blockIdx.x, nwg);
+    const int tn = lid % p.tiles_n, tm = lid / p.tiles_n;
+    const int m0 = tm * SBM, n0 = tn * SBN;
+
+    f32x16_t at[2][2], as[2][2];  // teacher / student, [n-block a][m-block b]
+    sgemm_tile(p.Qt, p.ldqt, p.N, p.Dt, p.lddt, p.G, p.dim_t, m0, n0, smem, tid, at);
+    sgemm_tile(p.Qs, p.ldqs, p.N, p.Ds, p.ldds, p.G, p.dim_s, m0, n0, smem, tid, as);
+
+    const float c2 = p.c * LOG2E;
+    if constexpr (MODE == SIMKL_FWD) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int m = m0 + wm * 64 + b * 32 + l31;
+            float mt = -INFINITY, ms = -INFINITY;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int n = n0 + wn * 64 + a * 32 + acc_row(r, hi);
+                    if (n < p.G) {
+                        mt = fmaxf(mt, at[a][b][r] * c2);
+                        ms = fmaxf(ms, as[a][b][r] * c2);
+                    }
+                }
+            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+            ms = fmaxf(ms, __shfl_xor(ms, 32, 64));
+            float lt = 0.f, ls = 0.f, aa = 0.f;
+            if (mt > -INFINITY) {   // (the slice has a column below G: then ms is finite too)
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int n = n0 + wn * 64 + a * 32 + acc_row(r, hi);
+                        // a column past G gives exactly 0 to all three sums: it is dropped BEFORE t - s, never as (-inf) - (-inf)
+                        const bool ok = n < p.G;
+                        const float et = ok ? exp2f(at[a][b][r] * c2 - mt) : 0.f;
+                        const float es = ok ? exp2f(as[a][b][r] * c2 - ms) : 0.f;
+                        const float df = ok ? (at[a][b][r] - as[a][b][r]) * p.c : 0.f;
+                        lt += et;
+                        ls += es;
+                        aa += et * df;
+                    }
+            }
+            lt += __shfl_xor(lt, 32, 64);
+            ls += __shfl_xor(ls, 32, 64);
+            aa += __shfl_xor(aa, 32, 64);
+            if (hi == 0 && m < p.N) {
+                const size_t o = (size_t)m * p.nparts + tn * 2 + wn;
+                p.pmt[o] = mt; p.plt[o] = lt; p.pat[o] = aa; p.pms[o] = ms; p.pls[o] = ls;
+            }
+        }
+    } else {
+        const float k = p.coef * p.c;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int m = m0 + wm * 64 + b * 32 + l31;
+            const bool m_ok = m < p.N;
+            const int mc = m_ok ? m : p.N - 1;
+            const float lt2 = p.lse_t[mc] * LOG2E, ls2 = p.lse_s[mc] * LOG2E;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int n = n0 + wn * 64 + a * 32 + 8 * q + 4 * hi;
+                    float g[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float qs = exp2f(as[a][b][4 * q + e] * c2 - ls2);
+                        const float pt = exp2f(at[a][b][4 * q + e] * c2 - lt2);
+                        const bool ok = m_ok && (n + e) < p.G;
+                        g[e] = ok ? (qs - pt) * k : 0.f;
+                        if (ok) p.GmT[(size_t)(n + e) * p.N + m] = g[e];
+                    }
+                    if (m_ok) {
+                        if (n + 3 < p.G) {
+                            *reinterpret_cast<float4*>(p.Gm + (size_t)m * p.G + n) = make_float4(g[0], g[1], g[2], g[3]);
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+                                if (n + e < p.G) p.Gm[(size_t)m * p.G + n + e] = g[e];
+                        }
+                    }
+                }
+        }
+    }
+}
+
+// One row's slices folded: *mx = the row maximum (log2 units), *l = sum_j exp2(v_j - mx), *a (with pa) = the third sum rescaled
+// the same way.  Called for the teacher and for the student: equal partials give equal bits.
+CX_DEVICE void simkl_fold(const float* __restrict__ pm, const float* __restrict__ pl, const float* __restrict__ pa,
+                          int nparts, int lane, float* mx_out, float* l_out, float* a_out) {
+    float mx = -INFINITY;
+    for (int i = lane; i < nparts; i += 64) mx = fmaxf(mx, pm[i]);
+    mx = wave_max(mx);
+    float l = 0.f, a = 0.f;
+    for (int i = lane; i < nparts; i += 64) {
+        const float m = pm[i];
+        if (m > -INFINITY) {
+            const float w = exp2f(m - mx);
+            l += pl[i] * w;
+            if (pa) a += pa[i] * w;
+        }
+    }
+    *mx_out = mx;
+    *l_out = wave_sum(l);
+    if (pa) *a_out = wave_sum(a);
+}
+
+// one wave per row.  kl = sum_j p_j (t_j - s_j) + (lse_s - lse_t); the difference of the two log-sum-exps is formed as
+// (m_s - m_t) + log2(l_s / l_t): its rounding error scales with the difference, not with the lse (a student close to its teacher
+// has kl << lse), and it is exactly 0 for equal partials.
+__global__ __launch_bounds__(256) void simkl_combine_kernel(const float* __restrict__ pmt, const float* __restrict__ plt,
+                                                            const float* __restrict__ pat, const float* __restrict__ pms,
+                                                            const float* __restrict__ pls, float* __restrict__ lse_s,
+                                                            float* __restrict__ lse_t, float* __restrict__ kl_rows, int N,
+                                                            int nparts) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= N) return;
+    const size_t o = (size_t)row * nparts;
+    float mt, lt, at = 0.f, ms, ls;
+    simkl_fold(pmt + o, plt + o, pat + o, nparts, lane, &mt, &lt, &at);
+    simkl_fold(pms + o, pls + o, nullptr, nparts, lane, &ms, &ls, nullptr);
+    if (lane == 0) {
+        lse_t[row] = (mt + log2f(lt)) * LN2;
+        lse_s[row] = (ms + log2f(ls)) * LN2;
+        kl_rows[row] = at / lt + ((ms - mt) + log2f(ls / lt)) * LN2;
+    }
+}
+
 template <int EPI>
 int launch(const SgemmParams& p, hipStream_t s) {
     hipLaunchKernelGGL((sgemm_nt_kernel<EPI>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
@@ -341,6 +506,66 @@ int cx_infonce_bwd(const float* Q, const float* D, const int64_t* labels, const 
     rc = cx_sgemm_nt(Gmat, DT, dQ, N, dim, G, G, G, dim, stream);   // dQ[m][c] = sum_n Gm[m][n] D[n][c]
     if (rc != CX_OK) return rc;
     return cx_sgemm_nt(GmatT, QT, dD, G, dim, N, N, N, dim, stream); // dD[n][c] = sum_m Gm[m][n] Q[m][c]
+}
+
+long cx_simkl_ws_floats(int N, int G) {
+    const long nparts = 2L * ((G + SBN - 1) / SBN);
+    return (long)N * 5 * nparts;
+}
+
+static int simkl_check(int N, int G, int dim_s, int dim_t, int ldqs, int ldds, int ldqt, int lddt) {
+    int rc = check_common(N, G, dim_s, ldqs, ldds);
+    if (rc != CX_OK) return rc;
+    return check_common(N, G, dim_t, ldqt, lddt);
+}
+
+static void simkl_fill(SimklParams& p, const float* Qs, const float* Ds, const float* Qt, const float* Dt, float inv_temp,
+                       int N, int G, int dim_s, int dim_t, int ldqs, int ldds, int ldqt, int lddt) {
+    p.Qs = Qs; p.Ds = Ds; p.Qt = Qt; p.Dt = Dt;
+    p.N = N; p.G = G; p.dim_s = dim_s; p.dim_t = dim_t; p.ldqs = ldqs; p.ldds = ldds; p.ldqt = ldqt; p.lddt = lddt;
+    p.tiles_m = (N + SBM - 1) / SBM; p.tiles_n = (G + SBN - 1) / SBN; p.nparts = 2 * p.tiles_n;
+    p.c = inv_temp;
+}
+
+int cx_simkl_fwd(const float* Qs, const float* Ds, const float* Qt, const float* Dt, float inv_temp, float* ws,
+                 float* lse_s, float* lse_t, float* kl_rows, int N, int G, int dim_s, int dim_t, int ldqs, int ldds,
+                 int ldqt, int lddt, void* stream) {
+    if (N <= 0 || G <= 0) return CX_OK;
+    if (!Qs || !Ds || !Qt || !Dt || !ws || !lse_s || !lse_t || !kl_rows) return CX_ERR_ARG;
+    int rc = simkl_check(N, G, dim_s, dim_t, ldqs, ldds, ldqt, lddt);
+    if (rc != CX_OK) return rc;
+    SimklParams p = {};
+    simkl_fill(p, Qs, Ds, Qt, Dt, inv_temp, N, G, dim_s, dim_t, ldqs, ldds, ldqt, lddt);
+    const size_t sz = (size_t)N * p.nparts;
+    p.pmt = ws; p.plt = ws + sz; p.pat = ws + 2 * sz; p.pms = ws + 3 * sz; p.pls = ws + 4 * sz;
+    hipLaunchKernelGGL((simkl_kernel<SIMKL_FWD>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    hipLaunchKernelGGL(simkl_combine_kernel, dim3((N + 3) / 4), dim3(256), 0, (hipStream_t)stream, p.pmt, p.plt, p.pat,
+                       p.pms, p.pls, lse_s, lse_t, kl_rows, N, p.nparts);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+int cx_simkl_bwd(const float* Qs, const float* Ds, const float* Qt, const float* Dt, const float* lse_s,
+                 const float* lse_t, float inv_temp, float coef, float* Gmat, float* GmatT, float* QsT, float* DsT,
+                 float* dQs, float* dDs, int N, int G, int dim_s, int dim_t, int ldqs, int ldds, int ldqt, int lddt,
+                 void* stream) {
+    if (N <= 0 || G <= 0) return CX_OK;
+    if (!Qs || !Ds || !Qt || !Dt || !lse_s || !lse_t || !Gmat || !GmatT || !QsT || !DsT || !dQs || !dDs) return CX_ERR_ARG;
+    int rc = simkl_check(N, G, dim_s, dim_t, ldqs, ldds, ldqt, lddt);
+    if (rc != CX_OK) return rc;
+    if ((N % 4) != 0 || (G % 4) != 0) return CX_ERR_SHAPE;  // they are the K (and ld) of the two output GEMMs
+    SimklParams p = {};
+    simkl_fill(p, Qs, Ds, Qt, Dt, inv_temp, N, G, dim_s, dim_t, ldqs, ldds, ldqt, lddt);
+    p.lse_s = lse_s; p.lse_t = lse_t; p.coef = coef; p.Gm = Gmat; p.GmT = GmatT;
+    hipLaunchKernelGGL((simkl_kernel<SIMKL_GRAD>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, (hipStream_t)stream, p);
+    if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    rc = cx_transpose_f32(Qs, QsT, N, dim_s, ldqs, N, stream);
+    if (rc != CX_OK) return rc;
+    rc = cx_transpose_f32(Ds, DsT, G, dim_s, ldds, G, stream);
+    if (rc != CX_OK) return rc;
+    rc = cx_sgemm_nt(Gmat, DsT, dQs, N, dim_s, G, G, G, dim_s, stream);   // dQs[m][c] = sum_n Gm[m][n] Ds[n][c]
+    if (rc != CX_OK) return rc;
+    return cx_sgemm_nt(GmatT, QsT, dDs, G, dim_s, N, N, N, dim_s, stream); // dDs[n][c] = sum_m Gm[m][n] Qs[m][c]
 }
 
 }  // extern "C"

@@ -245,6 +245,107 @@ def clip_loss(query, document, logit_scale, step=None, gather_enabled=False, tra
     return loss
 
 
+# ------------------------------------------------------------------------------------------------- distillation
+class _FusedSimKL(torch.autograd.Function):
+    """coef * sum_i KL(softmax_j t_ij || softmax_j s_ij)  for t = inv_temp * Qt Dt^T, s = inv_temp * Qs Ds^T, without either (N, G)
+    matrix (cx_simkl_fwd / cx_simkl_bwd).  Gradients for the student operands only."""
+
+    @staticmethod
+    def forward(ctx, sq: torch.Tensor, sd: torch.Tensor, tq: torch.Tensor, td: torch.Tensor, inv_temp: float, coef: float):
+        if not (sq.is_cuda and sd.is_cuda and tq.is_cuda and td.is_cuda):
+            raise RuntimeError("fused similarity-KL needs the HIP device path (no CPU fallback)")
+        lib = _C.lib()
+
+        def prep(t):
+            t = t.detach()
+            if t.dtype != torch.float32:
+                t = t.float()
+            return t if t.stride(-1) == 1 else t.contiguous()
+
+        sq, sd, tq, td = prep(sq), prep(sd), prep(tq), prep(td)
+        N, dim_s = sq.shape
+        G = sd.shape[0]
+        dim_t = tq.shape[1]
+        if tq.shape[0] != N or td.shape[0] != G or sd.shape[1] != dim_s or td.shape[1] != dim_t:
+            raise ValueError(f"similarity-KL: student {tuple(sq.shape)} x {tuple(sd.shape)} against teacher "
+                             f"{tuple(tq.shape)} x {tuple(td.shape)}")
+        if (dim_s % 4) or (dim_t % 4):
+            raise ValueError(f"fused similarity-KL needs widths that are multiples of 4 (got {dim_s}, {dim_t})")
+        if ((N % 4) or (G % 4)) and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            # the backward's two output GEMMs contract over N and G: fail here, not in the middle of loss.backward()
+            raise ValueError(f"fused similarity-KL backward needs N and G to be multiples of 4 (got {N}, {G})")
+        f32 = dict(dtype=torch.float32, device=sq.device)
+        ws = torch.empty(lib.cx_simkl_ws_floats(N, G), **f32)
+        lse_s, lse_t, rows = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, **f32)
+        _C.check(lib.cx_simkl_fwd(sq.data_ptr(), sd.data_ptr(), tq.data_ptr(), td.data_ptr(), inv_temp, ws.data_ptr(),
+                                  lse_s.data_ptr(), lse_t.data_ptr(), rows.data_ptr(), N, G, dim_s, dim_t, sq.stride(0),
+                                  sd.stride(0), tq.stride(0), td.stride(0), _C.cur_stream()), "cx_simkl_fwd")
+        ctx.save_for_backward(sq, sd, tq, td, lse_s, lse_t)
+        ctx.inv_temp, ctx.coef = inv_temp, coef
+        ctx.kl_rows = rows
+        return rows.sum() * coef
+
+    @staticmethod
+    def backward(ctx, gout):
+        sq, sd, tq, td, lse_s, lse_t = ctx.saved_tensors
+        lib = _C.lib()
+        N, dim_s = sq.shape
+        G = sd.shape[0]
+        f32 = dict(dtype=torch.float32, device=sq.device)
+        gm, gmt = torch.empty(N, G, **f32), torch.empty(G, N, **f32)
+        qt, dt = torch.empty(dim_s, N, **f32), torch.empty(dim_s, G, **f32)
+        dq, dd = torch.empty(N, dim_s, **f32), torch.empty(G, dim_s, **f32)
+        _C.check(lib.cx_simkl_bwd(sq.data_ptr(), sd.data_ptr(), tq.data_ptr(), td.data_ptr(), lse_s.data_ptr(),
+                                  lse_t.data_ptr(), ctx.inv_temp, ctx.coef, gm.data_ptr(), gmt.data_ptr(), qt.data_ptr(),
+                                  dt.data_ptr(), dq.data_ptr(), dd.data_ptr(), N, G, dim_s, tq.shape[1], sq.stride(0),
+                                  sd.stride(0), tq.stride(0), td.stride(0), _C.cur_stream()), "cx_simkl_bwd")
+        return dq * gout, dd * gout, None, None, None, None
+
+
+def similarity_kl_loss(student_q, student_d, teacher_q, teacher_d, temperature: float) -> torch.Tensor:
+    """F.kl_div(log_softmax(s), softmax(t), reduction="batchmean") for s = student_q student_d^T / temperature and
+    t = teacher_q teacher_d^T / temperature (sc/trainers/distill.py:348-355) as one fused kernel: no similarity matrix, no vendor BLAS.
+    The teacher operands are constants (no gradient); student and teacher widths are independent."""
+    temperature = float(temperature)
+    if not temperature > 0.0:
+        raise ValueError(f"distill temperature must be positive, got {temperature}")
+    return _FusedSimKL.apply(student_q, student_d, teacher_q, teacher_d, 1.0 / temperature, 1.0 / student_q.shape[0])
+
+
+def distill_loss(loss_fn: str, student_q, student_d, teacher_q, teacher_d, temperature: float) -> Dict[str, torch.Tensor]:
+    """The loss dictionary of sc/trainers/distill.py:341-385 from the four L2-normalised embedding matrices, keys included.
+    `kd`: the KL term is rank-local (not gathered) and weighted world * 1000; its InfoNCE companion is the reference's
+    infonce(q, d, 0.02) -- the literal 0.02, documents gathered, x world -- on the existing fused kernel.  `towers`: four InfoNCE
+    terms at scale 1 / temperature, the second argument gathered each time."""
+    inited = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size() if inited else 1
+    if loss_fn == "mse":
+        if student_q.shape[-1] != teacher_q.shape[-1] or student_d.shape[-1] != teacher_d.shape[-1]:
+            raise ValueError(f"distill_loss_fn 'mse' needs equal widths (student {student_q.shape[-1]}, teacher "
+                             f"{teacher_q.shape[-1]})")
+        query_mse = torch.nn.functional.mse_loss(student_q, teacher_q.detach())
+        document_mse = torch.nn.functional.mse_loss(student_d, teacher_d.detach())
+        return {"loss": query_mse + document_mse, "query_mse": query_mse, "document_mse": document_mse}
+    if loss_fn == "kd":
+        kd_loss = similarity_kl_loss(student_q, student_d, teacher_q, teacher_d, temperature)
+        infonce_loss = clip_loss(student_q, student_d, 50.0, gather_enabled=True)   # "hardcode temp to 50 for now" (distill.py:357)
+        return {"loss": world * 1000 * kd_loss + infonce_loss, "kd_loss": kd_loss, "infonce_loss": infonce_loss}
+    if loss_fn == "towers":
+        scale = 1.0 / float(temperature)
+        tq, td = teacher_q.detach(), teacher_d.detach()
+        student = clip_loss(student_q, student_d, scale, gather_enabled=True)     # q_s -> d_s
+        query = clip_loss(student_q, tq, scale, gather_enabled=True)              # q_s -> q_t
+        document = clip_loss(student_d, td, scale, gather_enabled=True)           # d_s -> d_t
+        teacher = clip_loss(student_q, td, scale, gather_enabled=True)            # q_s -> d_t
+        return {"loss": (student + query + document + teacher) / 4, "loss_infonce_student": student,
+                "loss_teacher_query": query, "loss_teacher_document": document, "loss_infonce_teacher": teacher}
+    if loss_fn == "stella":
+        raise NotImplementedError("distill_loss_fn 'stella': its triplet term differences every pair of pairwise scores "
+                                  "(sc/trainers/distill.py:302-307, 406-410), O(N^4) memory in the reference's own form; "
+                                  "served: mse, kd, towers")
+    raise NotImplementedError(f"Loss function {loss_fn} not implemented")
+
+
 # ----------------------------------------------------------------------------------------------------- GradCache
 def _split_inputs(inputs: Dict[str, torch.Tensor], chunk_size: int, tail_seqs: int = 0) -> List[Dict]:
     """Chunk a tower's input dict along the batch axis and attach host-side sequence lengths (one sync per tower).

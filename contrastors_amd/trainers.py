@@ -611,15 +611,21 @@ class ImageTextTrainer(TextTextTrainer):
         return out["loss"].detach()
 
 
-# sc/trainers/__init__.py:9-17 (the contrastive entries + MLM pretraining; glue / distill trainers are outside the hot path)
+# sc/trainers/__init__.py:9-17 (the contrastive entries, MLM pretraining and distillation; the glue trainer is outside the hot path)
 def _mlm_trainer(*a, **k):
     from .mlm import MLMTrainer  # imported lazily: mlm.py imports this module's schedule helper
 
     return MLMTrainer(*a, **k)
 
 
+def _distill_trainer(*a, **k):
+    from .distill import DistillTrainer  # imported lazily: distill.py imports this module's TextTextTrainer
+
+    return DistillTrainer(*a, **k)
+
+
 TRAINER_REGISTRY = {"encoder": TextTextTrainer, "image_text": ImageTextTrainer, "locked_text": ImageTextTrainer,
-                    "mlm": _mlm_trainer}
+                    "mlm": _mlm_trainer, "distill": _distill_trainer}
 
 
 def synthetic_batches(n_steps: int, per_rank_batch: int, seq_len: int, vocab: int = 30522, seed: int = 1234,

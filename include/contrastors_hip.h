@@ -376,6 +376,27 @@ int cx_rescore_topk(const uint16_t* Q, const uint16_t* D, const int64_t* cand, c
 int cx_infonce_bwd(const float* Q, const float* D, const int64_t* labels, const float* lse, float scale, float coef,
                    float* Gmat, float* GmatT, float* QT, float* DT, float* dQ, float* dD, float* dscale_accum,
                    int N, int G, int dim, int ldq, int ldd, void* stream);
+/* ---- fused similarity-KL: the `kd` term of the distillation trainer (sc/trainers/distill.py:347-355)
+ * F.kl_div(log_softmax(s), softmax(t), reduction="batchmean") * N, row by row, for t = inv_temp * Qt Dt^T (teacher) and
+ * s = inv_temp * Qs Ds^T (student):  kl_rows[i] = sum_j p_ij (t_ij - s_ij) - lse_t[i] + lse_s[i],  p = softmax_j t.
+ * Qs:(N,dim_s) ldqs, Ds:(G,dim_s) ldds, Qt:(N,dim_t) ldqt, Dt:(G,dim_t) lddt fp32; the widths are independent.  Both products
+ * of a 128 x 128 tile run on the exact-fp32 MFMA path of cx_infonce_fwd in one kernel; neither (N,G) matrix is written, no
+ * atomics (a repeated call gives the same bits; identical student and teacher operands give kl_rows == 0 exactly).
+ * ws: cx_simkl_ws_floats(N,G) floats.  Outputs: lse_s, lse_t, kl_rows:(N) fp32 (natural log).  The host takes sum / N.
+ * Requirements: dim_s % 4 == 0, dim_t % 4 == 0 (CX_ERR_SHAPE), every leading dimension % 4 == 0 (CX_ERR_ALIGN).
+ * Additive: cx_abi_version stays 10. */
+long cx_simkl_ws_floats(int N, int G);
+int cx_simkl_fwd(const float* Qs, const float* Ds, const float* Qt, const float* Dt, float inv_temp, float* ws,
+                 float* lse_s, float* lse_t, float* kl_rows, int N, int G, int dim_s, int dim_t, int ldqs, int ldds,
+                 int ldqt, int lddt, void* stream);
+/* backward of  coef * sum_i kl_rows[i]  with respect to the student only (the teacher is a constant, and so is inv_temp: no
+ * scale gradient, hence no atomic):  Gm[i][j] = coef * inv_temp * (q_ij - p_ij), q = softmax_j s, is written to Gmat:(N,G) and
+ * GmatT:(G,N) fp32 scratch; dQs:(N,dim_s) = Gm Ds, dDs:(G,dim_s) = Gm^T Qs (overwritten).  QsT:(dim_s,N), DsT:(dim_s,G) fp32
+ * scratch.  lse_s / lse_t: what cx_simkl_fwd wrote.  Requirements of the forward, and N % 4 == 0, G % 4 == 0 (CX_ERR_SHAPE). */
+int cx_simkl_bwd(const float* Qs, const float* Ds, const float* Qt, const float* Dt, const float* lse_s,
+                 const float* lse_t, float inv_temp, float coef, float* Gmat, float* GmatT, float* QsT, float* DsT,
+                 float* dQs, float* dDs, int N, int G, int dim_s, int dim_t, int ldqs, int ldds, int ldqt, int lddt,
+                 void* stream);
 /* ---- the same loss on the fp8 matrix-core path (BASELINE.json configs[4] "fp8 MFMA similarity GEMM"; the reference
  * only carries the `use_fp8` flag, configs/train/contrastive_pretrain.yaml:24).  Rows are quantised to OCP e4m3 with
  * one scale per row, the contraction is v_mfma_scale_f32_32x32x64_f8f6f4 (fp32 accumulate, online fp32 log-sum-exp);
