@@ -216,7 +216,7 @@ def test_transpose_and_casts():
 
 
 # ------------------------------------------------------------------------------------------------------- LayerNorm
-@pytest.mark.parametrize("d", [256, 768, 1024])
+@pytest.mark.parametrize("d", [256, 512, 768, 1024])
 @pytest.mark.parametrize("rows", [1, 1003])
 def test_layernorm_fwd_bwd(d, rows):
     x0, res = bf(_randn(rows, d, seed=10)), bf(_randn(rows, d, seed=11))
