@@ -51,14 +51,17 @@ CX_DEVICE void rotary_pair(float x1, float x2, float c, float s, float& o1, floa
 // Backward of act = y * silu(g) from the saved (act, gate) pair (round 3's compact save: y = act / silu(g) is recovered
 // inside the derivative):  d y = d * g * s,  d gate = d * y * silu'(g) = d * act * (1 / g + 1 - s),  s = sigmoid(g).
 // An exactly-zero gate (or a silu that underflowed) means act = 0, y is not recoverable and d gate comes out 0.  1 / g is
-// clamped to +-1e30 (one v_med3_f32: round 5): 0 * (clamped 1/0) = 0 with an ordinary multiply, and a denormal gate
+// clamped to +-FLT_MAX (one v_med3_f32: round 5): 0 * (clamped 1/0) = 0 with an ordinary multiply, and a denormal gate
 // next to a non-zero (denormal) act gives a finite d gate instead of inf * x -- round 4's legacy multiply covered act == 0 only.
 // No compare / select per element (the fc2-dgrad + SwiGLU-backward epilogue spends ~3200 VALU instructions per tile and wave in
-// the one wave that also issues the MFMAs).  Every |g| >= 1e-30 is untouched by the clamp: same bits as round 4 there.
+// the one wave that also issues the MFMAs).  Every normal g is untouched by the clamp: same bits as round 4 there.
 // NaN: v_med3_f32 returns a finite bound for a NaN 1/g, so a NaN GATE yields a finite (garbage) d gate here -- but d y = g * s * d is NaN for the
 // same element, and both leave in the same (T, 2I) gradient tensor that feeds the fc1 wgrad / dgrad: the non-finite value still reaches the
 // gradient norm the trainer checks.
-CX_DEVICE float rcp_clamped(float g) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(g), -1e30f, 1e30f); }
+// The clamp is +-FLT_MAX, not a smaller round number: 1 / g of the smallest NORMAL gates (|g| down to 2^-126, 1 / g = 2^126 = 8.5e37) must
+// pass untouched -- a bound of 1e30 turned d gate of a gate of 1.2e-38 into d * act * 1e30, eight orders too small
+// (tests/test_elementwise_edges_gpu.py, the saturation family).  Only the inf of a zero or denormal gate is clamped.
+CX_DEVICE float rcp_clamped(float g) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(g), -3.4028235e38f, 3.4028235e38f); }
 CX_DEVICE void swiglu_bwd_from_act(float d, float act, float g, float& dy, float& dg) {
     const float s = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g));
     dy = g * s * d;

@@ -70,10 +70,13 @@ __global__ __launch_bounds__(XB) void xent_fwd_kernel(const T* __restrict__ logi
         float mm = m;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) { v[e] *= scale; mm = fmaxf(mm, v[e]); }
-        float acc = s * __expf(m - mm);
+        // every logit seen so far is -inf: s stays 0 (m - mm and v - mm would be -inf - -inf = NaN; online_merge guards the same case)
+        if (mm != -INFINITY) {
+            float acc = s * __expf(m - mm);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) acc += __expf(v[e] - mm);
-        s = acc;
+            for (int e = 0; e < VEC; ++e) acc += __expf(v[e] - mm);
+            s = acc;
+        }
         m = mm;
     }
 #pragma unroll
