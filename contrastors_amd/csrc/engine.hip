@@ -11,6 +11,7 @@
 // single host call and the kernels queue back-to-back.
 #include <hip/hip_runtime.h>
 #include "../../include/contrastors_hip.h"
+#include "ln_workspace.h"
 
 namespace {
 
@@ -427,21 +428,16 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
         CX_TRY(wgrad(buf->g_wide, 3 * d, attn_in, d, w.gWqkv, buf, T, stream));
         return proj_residual(buf->g_wide, w.WqkvT, nullptr, add, buf->g_b, T, d, 3 * d, folded, stream, buf);
     };
+    // the third partial vector of a LayerNorm backward (the column sums of its dz / dx0) fits the arena's workspace
+    const bool ws_holds_colsum = cx_ln_bwd_ws_holds(buf->ws_f32, buf->ws_floats, 3, d);
     // LayerNorm backward whose dz is the gradient of (Linear output + residual): `gbias` (the Linear's bias gradient, may be
-    // NULL) rides along as the column sums of dz when the kernel has its workspace; *done says whether it did
+    // NULL) rides along as the column sums of dz when the workspace holds their partials; *done says whether it did
     auto ln_bwd = [&](const uint16_t* a, const uint16_t* b2, const uint16_t* z, const float* g, const float* mean,
                       const float* rstd, const uint16_t* dz_extra, uint16_t* dz, float* gg, float* gb, float* gbias,
                       bool* done) -> int {
-        *done = false;
-        if (gbias) {
-            const int rc = cx_layernorm_bwd_colsum(a, b2, z, g, mean, rstd, dz_extra, dz, gg, gb, gbias, buf->ws_f32,
-                                                   buf->ws_floats, T, d, stream);
-            if (rc != CX_ERR_ARG) {
-                *done = rc == CX_OK;
-                return rc;
-            }
-        }
-        return cx_layernorm_bwd(a, b2, z, g, mean, rstd, dz_extra, dz, gg, gb, buf->ws_f32, buf->ws_floats, T, d, stream);
+        *done = gbias && ws_holds_colsum;
+        return cx_layernorm_bwd_colsum(a, b2, z, g, mean, rstd, dz_extra, dz, gg, gb, *done ? gbias : nullptr, buf->ws_f32,
+                                       buf->ws_floats, T, d, stream);
     };
     // activation checkpointing (slot mode 2): the block's intermediates are recomputed from its saved input into slot 0
     // right before its backward (bit-identical: every kernel on the path is deterministic)
@@ -464,7 +460,7 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
 #ifdef CX_AB_R5_ROUTES
                 const bool cs = false;
 #else
-                const bool cs = buf->ws_f32 && buf->ws_floats >= 3L * d * 256;
+                const bool cs = ws_holds_colsum;
 #endif
                 CX_TRY(cx_dropout_add_layernorm_bwd_colsum(da, db, s.z2(l), w.ln2_g, s.mean2(l), s.rstd2(l), buf->g_c, buf->g_d, w.gln2_g,
                                                            w.gln2_b, cs ? w.gbfc2 : nullptr, buf->ws_f32, buf->ws_floats, T, d, p,
@@ -483,7 +479,7 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
             // LN2: dz2 = grad of (mlp_out + h1); its column sums are fc2's bias gradient
             bool b2_done = false, b1_done = false;
             if (pg && l == L - 1) {
-                const bool cs = w.gbfc2 && buf->ws_f32 && buf->ws_floats >= 3L * d * 256;
+                const bool cs = w.gbfc2 && ws_holds_colsum;
                 CX_TRY(cx_layernorm_bwd_pooled(pg->demb, pg->emb, pg->norm, cu_seqlens, Bc, pg->pool_mode, pg->normalize, s.z2(l),
                                                w.ln2_g, s.mean2(l), s.rstd2(l), buf->g_c, w.gln2_g, w.gln2_b,
                                                cs ? w.gbfc2 : nullptr, buf->ws_f32, buf->ws_floats, T, d, stream));
@@ -520,7 +516,7 @@ int blocks_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const S
     } else {
         float* gb_top = enc->layers[L - 1].gbfc2;
         if (pg) {
-            const bool cs = gb_top && buf->ws_f32 && buf->ws_floats >= 3L * d * 256;
+            const bool cs = gb_top && ws_holds_colsum;
             CX_TRY(cx_layernorm_bwd_pooled(pg->demb, pg->emb, pg->norm, cu_seqlens, Bc, pg->pool_mode, pg->normalize, buf->zf,
                                            enc->lnf_g, buf->meanf, buf->rstdf, buf->g_c, enc->glnf_g, enc->glnf_b,
                                            cs ? gb_top : nullptr, buf->ws_f32, buf->ws_floats, T, d, stream));

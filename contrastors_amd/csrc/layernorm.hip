@@ -4,29 +4,41 @@
 // the row held in registers.  Replaces flash_attn.ops.layer_norm.{dropout_add_layer_norm, layer_norm} at
 // sc/layers/block.py:422-431,453-462 and sc/models/encoder/modeling_nomic_bert.py:534 (dropout p = 0).
 #include "cx_common.h"
+#include "ln_workspace.h"
 #include "../../include/contrastors_hip.h"
 
 namespace {
 
-CX_DEVICE void load4_bf16(const bf16_t* p, float (&v)[4]) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
+CX_DEVICE void unpack4_bf16(const uint2 u, float (&v)[4]) {
     v[0] = bf16lo_to_f32(u.x); v[1] = bf16hi_to_f32(u.x);
     v[2] = bf16lo_to_f32(u.y); v[3] = bf16hi_to_f32(u.y);
 }
-CX_DEVICE void store4_bf16(bf16_t* p, const float (&v)[4]) {
+CX_DEVICE void load4_bf16(const bf16_t* p, float (&v)[4]) { unpack4_bf16(*reinterpret_cast<const uint2*>(p), v); }
+CX_DEVICE uint2 store4_bf16(bf16_t* p, const float (&v)[4]) {   // returns what it stored
     uint2 u;
     u.x = pack_bf16x2(v[0], v[1]);
     u.y = pack_bf16x2(v[2], v[3]);
     *reinterpret_cast<uint2*>(p) = u;
+    return u;
 }
 CX_DEVICE void load4_f32(const float* p, float (&v)[4]) {
     const float4 u = *reinterpret_cast<const float4*>(p);
     v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
 }
-
-CX_DEVICE void unpack4_bf16(const uint2 u, float (&v)[4]) {
-    v[0] = bf16lo_to_f32(u.x); v[1] = bf16hi_to_f32(u.x);
-    v[2] = bf16lo_to_f32(u.y); v[3] = bf16hi_to_f32(u.y);
+// Store as bf16 and add what was STORED (the rounded values) to the column sums dc: the bias gradient sums what the next
+// kernels read, like the standalone cx_bias_grad pass did.
+CX_DEVICE void store4_bf16_sum(bf16_t* p, const float (&v)[4], float (&dc)[4]) {
+    float r[4];
+    unpack4_bf16(store4_bf16(p, v), r);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dc[e] += r[e];
+}
+template <int N>
+CX_DEVICE void zero_acc(float (&a)[N][4]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a[i][e] = 0.f;
 }
 // Raw (packed bf16) row fetch, issued one row ahead of its use: with one 1.5 KiB row per wave and ~16 waves per CU the
 // kernels had only ~24-36 KiB in flight per CU, well short of what latency x HBM bandwidth asks for (~60 KiB).
@@ -37,6 +49,8 @@ CX_DEVICE void fetch_row(const bf16_t* __restrict__ base, int row, int lane, uin
         raw[i] = *reinterpret_cast<const uint2*>(base + (size_t)row * (NCH * 256) + (i * 64 + lane) * 4);
 }
 
+CX_DEVICE float wave_mean(float v, int d) { return wave_sum(v) / (float)d; }
+
 template <int NCH>
 CX_DEVICE void row_stats(const float (&z)[NCH][4], int d, float eps, float& mean, float& rstd) {
     float s = 0.f;
@@ -44,7 +58,7 @@ CX_DEVICE void row_stats(const float (&z)[NCH][4], int d, float eps, float& mean
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) s += z[i][e];
-    mean = wave_sum(s) / (float)d;
+    mean = wave_mean(s, d);
     float v = 0.f;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
@@ -53,8 +67,27 @@ CX_DEVICE void row_stats(const float (&z)[NCH][4], int d, float eps, float& mean
             const float c = z[i][e] - mean;
             v += c * c;
         }
-    rstd = rsqrtf(wave_sum(v) / (float)d + eps);
+    rstd = rsqrtf(wave_mean(v, d) + eps);
 }
+
+// The row math of every kernel below, per element.  Scalars by value on purpose: with the 4-element arrays passed by
+// reference the compiler kept them as vectors through the inlining, and ln_bwd_kernel<3, false>, which sits on its
+// 128-register budget, spilled.
+// Forward.
+CX_DEVICE float ln_affine(float z, float mean, float rstd, float g, float b) { return (z - mean) * rstd * g + b; }
+// Backward, first half: returns xh = the normalised z (kept for the second half) and adds the element's share to the row
+// sums s1 = sum(g dy xh), s2 = sum(g dy) and to the column's dgamma / dbeta.
+CX_DEVICE float ln_bwd_accum(float zz, float g, float dy, float mean, float rstd, float& s1, float& s2, float& dg, float& db) {
+    const float xh = (zz - mean) * rstd;
+    const float wdy = g * dy;
+    s1 += wdy * xh;
+    s2 += wdy;
+    dg += dy * xh;
+    db += dy;
+    return xh;
+}
+// Backward, second half, with s1 / s2 = wave_mean of the row sums (RMSNorm: s2 = 0).
+CX_DEVICE float ln_bwd_dz(float g, float dy, float xh, float s1, float s2, float rstd) { return (g * dy - s1 * xh - s2) * rstd; }
 
 template <int NCH>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ x0, const bf16_t* __restrict__ res,
@@ -100,7 +133,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
             const size_t off = (size_t)row * D + (i * 64 + lane) * 4;
             float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (z[i][e] - mean) * rstd * g[i][e] + b[i][e];
+            for (int e = 0; e < 4; ++e) o[e] = ln_affine(z[i][e], mean, rstd, g[i][e], b[i][e]);
             store4_bf16(out + off, o);
             if (z_out) store4_bf16(z_out + off, z[i]);
         }
@@ -111,11 +144,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const bf16_t* __restrict__ 
     }
 }
 
-// Shared tail of both backward kernels: fold the per-wave dgamma/dbeta partials of one block and atomically add.
-// Two-stage variant used when the caller provides a workspace: block `blk` writes its column partials to
-// part[blk][0..D) (dgamma) and part[blk][D..2D) (dbeta) with plain stores; ln_param_reduce_kernel sums the blocks.
+// Shared tail of the backward kernels: fold the per-wave dgamma / dbeta partials of one block through LDS
+// (smem: [2][4][D]).  Without a workspace (part == NULL) the block adds its column sums atomically; with one, block `blk`
+// writes them to part[blk][0..D) (dgamma) and part[blk][D..2D) (dbeta) with plain stores and ln_param_reduce_kernel sums
+// the blocks (deterministic).
 template <int NCH>
-CX_DEVICE void store_param_partials(float (&dg)[NCH][4], float (&db)[NCH][4], float* part, float* smem) {
+CX_DEVICE void fold_param_grads(float (&dg)[NCH][4], float (&db)[NCH][4], float* dgamma, float* dbeta, float* part,
+                                float* smem) {
     constexpr int D = NCH * 256;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -126,17 +161,30 @@ CX_DEVICE void store_param_partials(float (&dg)[NCH][4], float (&db)[NCH][4], fl
             smem[(1 * 4 + wave) * D + (i * 64 + lane) * 4 + e] = db[i][e];
         }
     __syncthreads();
-    float* mine = part + (size_t)blockIdx.x * 2 * D;
-    for (int c = threadIdx.x; c < 2 * D; c += 256) {
-        const int which = c / D, col = c - which * D;
-        float sacc = 0.f;
+    if (part) {
+        float* mine = part + (size_t)blockIdx.x * 2 * D;
+        for (int c = threadIdx.x; c < 2 * D; c += 256) {
+            const int which = c / D, col = c - which * D;
+            float sacc = 0.f;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) sacc += smem[(which * 4 + w) * D + col];
-        mine[c] = sacc;
+            for (int w = 0; w < 4; ++w) sacc += smem[(which * 4 + w) * D + col];
+            mine[c] = sacc;
+        }
+    } else {
+        for (int c = threadIdx.x; c < D; c += 256) {
+            float sg = 0.f, sb = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                sg += smem[(0 * 4 + w) * D + c];
+                sb += smem[(1 * 4 + w) * D + c];
+            }
+            if (dgamma) unsafeAtomicAdd(dgamma + c, sg);
+            if (dbeta) unsafeAtomicAdd(dbeta + c, sb);
+        }
     }
 }
 // third vector of a backward that also returns the column sums of its dz (the bias gradient of the Linear whose output
-// the LayerNorm consumed): block partials in part3[blk][D], folded by ln_param_reduce_kernel like the other two
+// the LayerNorm consumed): block partials in part3[blk][D], folded by colsum_reduce_kernel like the other two
 template <int NCH>
 CX_DEVICE void store_colsum_partials(float (&dc)[NCH][4], float* part3, float* smem) {
     constexpr int D = NCH * 256;
@@ -150,61 +198,44 @@ CX_DEVICE void store_colsum_partials(float (&dc)[NCH][4], float* part3, float* s
     float* mine = part3 + (size_t)blockIdx.x * D;
     for (int c = threadIdx.x; c < D; c += 256) mine[c] = smem[c] + smem[D + c] + smem[2 * D + c] + smem[3 * D + c];
 }
-__global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restrict__ part3, float* dst, int nblocks, int D) {
+// The tail of a backward kernel that may run with a workspace (part) and may sum the columns of what it wrote (CS).
+template <int NCH, bool CS>
+CX_DEVICE void finish_param_grads(float (&dg)[NCH][4], float (&db)[NCH][4], float (&dc)[CS ? NCH : 1][4], float* dgamma,
+                                  float* dbeta, float* part, float* part3, float* smem) {
+    fold_param_grads<NCH>(dg, db, dgamma, dbeta, part, smem);
+    if constexpr (CS) store_colsum_partials<NCH>(dc, part3, smem);
+}
+
+// Second stage of the workspace route, 64 columns x 4 block-groups per workgroup: each thread sums every 4th block's
+// partial for its column (independent, unrolled loads), then the 4 groups are folded through LDS.  True for the thread
+// that holds column `col`'s total over part[nblocks][ncols].
+CX_DEVICE bool fold_block_partials(const float* __restrict__ part, int nblocks, int ncols, int& col, float& tot) {
     __shared__ float red[4][64];
-    const int col = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
+    const int grp = threadIdx.x >> 6;
+    col = blockIdx.x * 64 + (threadIdx.x & 63);
     float sacc = 0.f;
-    if (col < D) {
+    if (col < ncols) {
 #pragma unroll 4
-        for (int b = grp; b < nblocks; b += 4) sacc += part3[(size_t)b * D + col];
+        for (int b = grp; b < nblocks; b += 4) sacc += part[(size_t)b * ncols + col];
     }
     red[grp][threadIdx.x & 63] = sacc;
     __syncthreads();
-    if (grp == 0 && col < D) dst[col] += red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if (grp != 0 || col >= ncols) return false;
+    tot = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    return true;
 }
-
-// 64 columns x 4 block-groups per workgroup: each thread sums every 4th block's partial for its column (independent,
-// unrolled loads), then the 4 groups are folded through LDS.
+__global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restrict__ part3, float* dst, int nblocks, int D) {
+    int col;
+    float tot;
+    if (fold_block_partials(part3, nblocks, D, col, tot)) dst[col] += tot;
+}
 __global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __restrict__ part, float* dgamma, float* dbeta,
                                                               int nblocks, int D) {
-    __shared__ float red[4][64];
-    const int col = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-    float sacc = 0.f;
-    if (col < 2 * D) {
-#pragma unroll 4
-        for (int b = grp; b < nblocks; b += 4) sacc += part[(size_t)b * 2 * D + col];
-    }
-    red[grp][threadIdx.x & 63] = sacc;
-    __syncthreads();
-    if (grp == 0 && col < 2 * D) {
-        const float tot = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    int col;
+    float tot;
+    if (fold_block_partials(part, nblocks, 2 * D, col, tot)) {
         float* dst = col < D ? dgamma : dbeta;
         if (dst) dst[col < D ? col : col - D] += tot;
-    }
-}
-
-template <int NCH>
-CX_DEVICE void flush_param_grads(float (&dg)[NCH][4], float (&db)[NCH][4], float* dgamma, float* dbeta,
-                                 float* smem /* [2][4][D] */) {
-    constexpr int D = NCH * 256;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            smem[(0 * 4 + wave) * D + (i * 64 + lane) * 4 + e] = dg[i][e];
-            smem[(1 * 4 + wave) * D + (i * 64 + lane) * 4 + e] = db[i][e];
-        }
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += 256) {
-        float sg = 0.f, sb = 0.f;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            sg += smem[(0 * 4 + w) * D + c];
-            sb += smem[(1 * 4 + w) * D + c];
-        }
-        if (dgamma) unsafeAtomicAdd(dgamma + c, sg);
-        if (dbeta) unsafeAtomicAdd(dbeta + c, sb);
     }
 }
 
@@ -224,14 +255,8 @@ __global__ __launch_bounds__(256, CS ? 3 : 4) void ln_bwd_kernel(const bf16_t* _
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float g[NCH][4], dg[NCH][4], db[NCH][4], dc[CS ? NCH : 1][4];
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dg[i][e] = db[i][e] = 0.f;
-            if (CS) dc[i][e] = 0.f;
-        }
-    }
+    for (int i = 0; i < NCH; ++i) load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
+    zero_acc(dg), zero_acc(db), zero_acc(dc);
     const int stride = gridDim.x * 4;
     int row = blockIdx.x * 4 + wave;
     uint2 na[NCH], nb[NCH], nz[NCH];
@@ -259,14 +284,8 @@ __global__ __launch_bounds__(256, CS ? 3 : 4) void ln_bwd_kernel(const bf16_t* _
             float zz[4];
             unpack4_bf16(nz[i], zz);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xh[i][e] = (zz[e] - mean) * rstd;
-                const float wdy = g[i][e] * dy[i][e];
-                s1 += wdy * xh[i][e];
-                s2 += wdy;
-                dg[i][e] += dy[i][e] * xh[i][e];
-                db[i][e] += dy[i][e];
-            }
+            for (int e = 0; e < 4; ++e)
+                xh[i][e] = ln_bwd_accum(zz[e], g[i][e], dy[i][e], mean, rstd, s1, s2, dg[i][e], db[i][e]);
         }
         if (row + stride < rows) {  // next row's loads fly under this row's reductions and stores
             fetch_row<NCH>(da, row + stride, lane, na);
@@ -275,40 +294,25 @@ __global__ __launch_bounds__(256, CS ? 3 : 4) void ln_bwd_kernel(const bf16_t* _
             nmean = mean_i[row + stride];
             nrstd = rstd_i[row + stride];
         }
-        s1 = wave_sum(s1) / (float)D;
-        s2 = wave_sum(s2) / (float)D;
+        s1 = wave_mean(s1, D);
+        s2 = wave_mean(s2, D);
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const size_t off = (size_t)row * D + (i * 64 + lane) * 4;
             float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (g[i][e] * dy[i][e] - s1 * xh[i][e] - s2) * rstd;
+            for (int e = 0; e < 4; ++e) o[e] = ln_bwd_dz(g[i][e], dy[i][e], xh[i][e], s1, s2, rstd);
             if (dz_extra) {
                 float t[4];
                 load4_bf16(dz_extra + off, t);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] += t[e];
             }
-            if constexpr (CS) {
-                uint2 u;
-                u.x = pack_bf16x2(o[0], o[1]);
-                u.y = pack_bf16x2(o[2], o[3]);
-                *reinterpret_cast<uint2*>(dz + off) = u;
-                float r[4];
-                unpack4_bf16(u, r);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dc[i][e] += r[e];
-            } else {
-                store4_bf16(dz + off, o);
-            }
+            if constexpr (CS) store4_bf16_sum(dz + off, o, dc[i]);
+            else store4_bf16(dz + off, o);
         }
     }
-    if (part) {
-        store_param_partials<NCH>(dg, db, part, smem);
-    } else {
-        flush_param_grads<NCH>(dg, db, dgamma, dbeta, smem);
-    }
-    if constexpr (CS) store_colsum_partials<NCH>(dc, part3, smem);
+    finish_param_grads<NCH, CS>(dg, db, dc, dgamma, dbeta, part, part3, smem);
 }
 
 // Backward of the LAST LayerNorm of a pooled encoder with the pooling backward folded in (round 3).  The gradient of the
@@ -333,14 +337,8 @@ __global__ __launch_bounds__(256, CS ? 3 : 4) void ln_bwd_pooled_kernel(const fl
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float g[NCH][4], dg[NCH][4], db[NCH][4], dc[CS ? NCH : 1][4];
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dg[i][e] = db[i][e] = 0.f;
-            if (CS) dc[i][e] = 0.f;
-        }
-    }
+    for (int i = 0; i < NCH; ++i) load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
+    zero_acc(dg), zero_acc(db), zero_acc(dc);
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
         const int t0 = cu[b], len = cu[b + 1] - t0;
         if (len <= 0) continue;  // (uniform per workgroup)
@@ -379,42 +377,24 @@ __global__ __launch_bounds__(256, CS ? 3 : 4) void ln_bwd_pooled_kernel(const fl
                 float zz[4];
                 load4_bf16(z + (size_t)row * D + (i * 64 + lane) * 4, zz);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    xh[i][e] = (zz[e] - mean) * rstd;
-                    const float wdy = g[i][e] * dy[i][e];
-                    s1 += wdy * xh[i][e];
-                    s2 += wdy;
-                    dg[i][e] += dy[i][e] * xh[i][e];
-                    db[i][e] += dy[i][e];
-                }
+                for (int e = 0; e < 4; ++e)
+                    xh[i][e] = ln_bwd_accum(zz[e], g[i][e], dy[i][e], mean, rstd, s1, s2, dg[i][e], db[i][e]);
             }
-            s1 = wave_sum(s1) / (float)D;
-            s2 = wave_sum(s2) / (float)D;
+            s1 = wave_mean(s1, D);
+            s2 = wave_mean(s2, D);
 #pragma unroll
             for (int i = 0; i < NCH; ++i) {
                 float o[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (g[i][e] * dy[i][e] - s1 * xh[i][e] - s2) * rstd;
-                uint2 u;
-                u.x = pack_bf16x2(o[0], o[1]);
-                u.y = pack_bf16x2(o[2], o[3]);
-                *reinterpret_cast<uint2*>(dz + (size_t)row * D + (i * 64 + lane) * 4) = u;
-                if (CS) {
-                    float r[4];
-                    unpack4_bf16(u, r);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) dc[i][e] += r[e];
-                }
+                for (int e = 0; e < 4; ++e) o[e] = ln_bwd_dz(g[i][e], dy[i][e], xh[i][e], s1, s2, rstd);
+                bf16_t* dst = dz + (size_t)row * D + (i * 64 + lane) * 4;
+                if constexpr (CS) store4_bf16_sum(dst, o, dc[i]);
+                else store4_bf16(dst, o);
             }
         }
         __syncthreads();  // g and red are rewritten for the next sequence
     }
-    if (part) {
-        store_param_partials<NCH>(dg, db, part, smem);
-    } else {
-        flush_param_grads<NCH>(dg, db, dgamma, dbeta, smem);
-    }
-    if constexpr (CS) store_colsum_partials<NCH>(dc, part3, smem);
+    finish_param_grads<NCH, CS>(dg, db, dc, dgamma, dbeta, part, part3, smem);
 }
 
 template <int NCH>
@@ -461,7 +441,7 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
         for (int i = 0; i < NCH; ++i) {
             float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (z[i][e] - mean) * rstd * g[i][e] + b[i][e];
+            for (int e = 0; e < 4; ++e) o[e] = ln_affine(z[i][e], mean, rstd, g[i][e], b[i][e]);
             store4_bf16(out + (size_t)t * D + (i * 64 + lane) * 4, o);
         }
         if (lane == 0) {
@@ -486,9 +466,8 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
     for (int i = 0; i < NCH; ++i) {
         load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
         load4_f32(type0 + (i * 64 + lane) * 4, ty[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dg[i][e] = db[i][e] = dty[i][e] = 0.f;
     }
+    zero_acc(dg), zero_acc(db), zero_acc(dty);
     for (int t = blockIdx.x * 4 + wave; t < T; t += gridDim.x * 4) {
         const int flat = indices[t];
         const long id = ids[flat];
@@ -515,25 +494,20 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
                 for (int e = 0; e < 4; ++e) zz[e] += pe[e];
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                zz[e] += ty[i][e];
-                xh[i][e] = (zz[e] - mean) * rstd;
-                const float wdy = g[i][e] * dy[i][e];
-                s1 += wdy * xh[i][e];
-                s2 += wdy;
-                dg[i][e] += dy[i][e] * xh[i][e];
-                db[i][e] += dy[i][e];
-            }
+            for (int e = 0; e < 4; ++e) zz[e] += ty[i][e];
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                xh[i][e] = ln_bwd_accum(zz[e], g[i][e], dy[i][e], mean, rstd, s1, s2, dg[i][e], db[i][e]);
         }
-        s1 = wave_sum(s1) / (float)D;
-        s2 = wave_sum(s2) / (float)D;
+        s1 = wave_mean(s1, D);
+        s2 = wave_mean(s2, D);
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const int col = (i * 64 + lane) * 4;
             float ov[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float o = (g[i][e] * dy[i][e] - s1 * xh[i][e] - s2) * rstd;
+                const float o = ln_bwd_dz(g[i][e], dy[i][e], xh[i][e], s1, s2, rstd);
                 ov[e] = o;
                 dty[i][e] += o;
                 // nn.Embedding(padding_idx=...) gives that row no gradient (sc/layers/embedding.py:581)
@@ -546,15 +520,12 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
             if (dz_out) *reinterpret_cast<float4*>(dz_out + (size_t)t * D + col) = make_float4(ov[0], ov[1], ov[2], ov[3]);
         }
     }
-    flush_param_grads<NCH>(dg, db, dgamma, dbeta, smem);
+    fold_param_grads<NCH>(dg, db, dgamma, dbeta, nullptr, smem);
     __syncthreads();
     // type-embedding row 0 receives the sum over every token: reuse the same block fold.
     float zero[NCH][4];
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) zero[i][e] = 0.f;
-    flush_param_grads<NCH>(dty, zero, dtype0, nullptr, smem);
+    zero_acc(zero);
+    fold_param_grads<NCH>(dty, zero, dtype0, nullptr, nullptr, smem);
 }
 
 // Word-embedding gradient without atomics (the scatter of 100 M fp32 atomics cost 1.4 ms per 131072-token chunk and made the
@@ -585,10 +556,7 @@ __global__ __launch_bounds__(256) void embed_scatter_sorted_kernel(const float* 
         const int n = lo2 - lo;
         if (n == 0) continue;     // (uniform over the workgroup: no barrier is skipped by part of it)
         float acc[NCH][4];
-#pragma unroll
-        for (int i = 0; i < NCH; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][e] = 0.f;
+        zero_acc(acc);
         for (int k = wave; k < n; k += 4) {
             const int t = perm[lo + k];
 #pragma unroll
@@ -665,7 +633,7 @@ __global__ __launch_bounds__(256) void ln_fwd_mixed_kernel(const void* __restric
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v += z[i][e] * z[i][e];
             mean = 0.f;
-            rstd = rsqrtf(wave_sum(v) / (float)D + eps);
+            rstd = rsqrtf(wave_mean(v, D) + eps);
         } else {
             row_stats<NCH>(z, D, eps, mean, rstd);
         }
@@ -676,7 +644,7 @@ __global__ __launch_bounds__(256) void ln_fwd_mixed_kernel(const void* __restric
             load4_f32(gamma + (i * 64 + lane) * 4, g);
             if (beta) load4_f32(beta + (i * 64 + lane) * 4, b);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (z[i][e] - mean) * rstd * g[e] + b[e];
+            for (int e = 0; e < 4; ++e) o[e] = ln_affine(z[i][e], mean, rstd, g[e], b[e]);
             store4_any(out, flags & LNF_OUT_F32, off, o);
             if (z_out) store4_any(z_out, flags & LNF_Z_F32, off, z[i]);  // statistics use the unrounded fp32 sum (as upstream)
         }
@@ -699,11 +667,8 @@ __global__ __launch_bounds__(256) void ln_bwd_mixed_kernel(const void* __restric
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float g[NCH][4], dg[NCH][4], db[NCH][4];
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dg[i][e] = db[i][e] = 0.f;
-    }
+    for (int i = 0; i < NCH; ++i) load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
+    zero_acc(dg), zero_acc(db);
     for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
         const float mean = mean_i[row], rstd = rstd_i[row];
         float dy[NCH][4], xh[NCH][4];
@@ -715,23 +680,17 @@ __global__ __launch_bounds__(256) void ln_bwd_mixed_kernel(const void* __restric
             float zz[4];
             load4_any(z, flags & LNF_Z_F32, off, zz);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xh[i][e] = (zz[e] - mean) * rstd;
-                const float wdy = g[i][e] * dy[i][e];
-                s1 += wdy * xh[i][e];
-                s2 += wdy;
-                dg[i][e] += dy[i][e] * xh[i][e];
-                db[i][e] += dy[i][e];
-            }
+            for (int e = 0; e < 4; ++e)
+                xh[i][e] = ln_bwd_accum(zz[e], g[i][e], dy[i][e], mean, rstd, s1, s2, dg[i][e], db[i][e]);
         }
-        s1 = wave_sum(s1) / (float)D;
-        s2 = (flags & LNF_RMS) ? 0.f : wave_sum(s2) / (float)D;   // RMSNorm has no mean to differentiate through (mean_i = 0)
+        s1 = wave_mean(s1, D);
+        s2 = (flags & LNF_RMS) ? 0.f : wave_mean(s2, D);   // RMSNorm has no mean to differentiate through (mean_i = 0)
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const size_t off = (size_t)row * D + (i * 64 + lane) * 4;
             float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (g[i][e] * dy[i][e] - s1 * xh[i][e] - s2) * rstd;
+            for (int e = 0; e < 4; ++e) o[e] = ln_bwd_dz(g[i][e], dy[i][e], xh[i][e], s1, s2, rstd);
             if (dz_extra) {
                 float t[4];
                 load4_any(dz_extra, flags & LNF_Z_F32, off, t);
@@ -742,7 +701,7 @@ __global__ __launch_bounds__(256) void ln_bwd_mixed_kernel(const void* __restric
             if (dres) store4_any(dres, flags & LNF_RES_F32, off, o);
         }
     }
-    flush_param_grads<NCH>(dg, db, dgamma, dbeta, smem);
+    fold_param_grads<NCH>(dg, db, dgamma, dbeta, nullptr, smem);
 }
 
 // ---- dropout > 0 (K5 dropout_add_layer_norm(p > 0), BertEmbeddings dropout): z = dropout_p(x0) + residual.  The mask is
@@ -777,7 +736,7 @@ __global__ __launch_bounds__(256) void ln_fwd_drop_kernel(const bf16_t* __restri
             load4_f32(gamma + (i * 64 + lane) * 4, g);
             load4_f32(beta + (i * 64 + lane) * 4, b);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (z[i][e] - mean) * rstd * g[e] + b[e];
+            for (int e = 0; e < 4; ++e) o[e] = ln_affine(z[i][e], mean, rstd, g[e], b[e]);
             store4_bf16(out + off, o);
             if (z_out) store4_bf16(z_out + off, z[i]);
         }
@@ -802,14 +761,8 @@ __global__ __launch_bounds__(256) void ln_bwd_drop_kernel(const bf16_t* __restri
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float g[NCH][4], dg[NCH][4], db[NCH][4], dc[CS ? NCH : 1][4];
 #pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-        load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            dg[i][e] = db[i][e] = 0.f;
-            if (CS) dc[i][e] = 0.f;
-        }
-    }
+    for (int i = 0; i < NCH; ++i) load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
+    zero_acc(dg), zero_acc(db), zero_acc(dc);
     for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
         const float mean = mean_i[row], rstd = rstd_i[row];
         float dy[NCH][4], xh[NCH][4];
@@ -827,47 +780,26 @@ __global__ __launch_bounds__(256) void ln_bwd_drop_kernel(const bf16_t* __restri
             float zz[4];
             load4_bf16(z + off, zz);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                xh[i][e] = (zz[e] - mean) * rstd;
-                const float wdy = g[i][e] * dy[i][e];
-                s1 += wdy * xh[i][e];
-                s2 += wdy;
-                dg[i][e] += dy[i][e] * xh[i][e];
-                db[i][e] += dy[i][e];
-            }
+            for (int e = 0; e < 4; ++e)
+                xh[i][e] = ln_bwd_accum(zz[e], g[i][e], dy[i][e], mean, rstd, s1, s2, dg[i][e], db[i][e]);
         }
-        s1 = wave_sum(s1) / (float)D;
-        s2 = wave_sum(s2) / (float)D;
+        s1 = wave_mean(s1, D);
+        s2 = wave_mean(s2, D);
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             const size_t off = (size_t)row * D + (i * 64 + lane) * 4;
             float o[4], keep[4], m[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (g[i][e] * dy[i][e] - s1 * xh[i][e] - s2) * rstd;
+            for (int e = 0; e < 4; ++e) o[e] = ln_bwd_dz(g[i][e], dy[i][e], xh[i][e], s1, s2, rstd);
             dropout_keep4(dr, site, off >> 2, keep);
 #pragma unroll
             for (int e = 0; e < 4; ++e) m[e] = o[e] * keep[e];
             store4_bf16(dz + off, o);
-            if constexpr (CS) {
-                uint2 u;
-                u.x = pack_bf16x2(m[0], m[1]);
-                u.y = pack_bf16x2(m[2], m[3]);
-                *reinterpret_cast<uint2*>(dx0 + off) = u;
-                float r[4];
-                unpack4_bf16(u, r);   // (the bias gradient sums what the next kernels read: the bf16 dx0)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) dc[i][e] += r[e];
-            } else {
-                store4_bf16(dx0 + off, m);
-            }
+            if constexpr (CS) store4_bf16_sum(dx0 + off, m, dc[i]);
+            else store4_bf16(dx0 + off, m);
         }
     }
-    if (part) {
-        store_param_partials<NCH>(dg, db, part, smem);
-    } else {
-        flush_param_grads<NCH>(dg, db, dgamma, dbeta, smem);
-    }
-    if constexpr (CS) store_colsum_partials<NCH>(dc, part3, smem);
+    finish_param_grads<NCH, CS>(dg, db, dc, dgamma, dbeta, part, part3, smem);
 }
 
 // x <- x * mask / (1 - p) in place (the embedding dropout on the embedding-LayerNorm output, and on its incoming gradient)
@@ -897,14 +829,19 @@ inline int ln_grid(int rows) {
 }
 inline int done() { return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
 
-#define CX_LN_DISPATCH(d, CALL)                     \
-    switch (d) {                                    \
-        case 256: { constexpr int NCH = 1; CALL; break; }  \
-        case 512: { constexpr int NCH = 2; CALL; break; }  \
-        case 768: { constexpr int NCH = 3; CALL; break; }  \
-        case 1024: { constexpr int NCH = 4; CALL; break; } \
-        default: return CX_ERR_SHAPE;               \
+// (variadic: a hipLaunchKernelGGL passed through a second macro arrives expanded, its commas bare)
+#define CX_LN_DISPATCH(d, ...)                                     \
+    switch (d) {                                                   \
+        case 256: { constexpr int NCH = 1; __VA_ARGS__; break; }   \
+        case 512: { constexpr int NCH = 2; __VA_ARGS__; break; }   \
+        case 768: { constexpr int NCH = 3; __VA_ARGS__; break; }   \
+        case 1024: { constexpr int NCH = 4; __VA_ARGS__; break; }  \
+        default: return CX_ERR_SHAPE;                              \
     }
+// the same for kernels that also take CS (sum the columns of what they write) as a template parameter
+#define CX_LN_DISPATCH_CS(d, cs, ...)                                       \
+    if (cs) { constexpr bool CS = true; CX_LN_DISPATCH(d, __VA_ARGS__); }   \
+    else { constexpr bool CS = false; CX_LN_DISPATCH(d, __VA_ARGS__); }
 
 }  // namespace
 
@@ -922,6 +859,42 @@ int cx_layernorm_fwd(const uint16_t* x0, const uint16_t* residual, const float* 
 }
 
 namespace {
+// Launch plan of the backward kernels.  With a workspace: many blocks (bandwidth) + deterministic two-stage reduction of the
+// parameter gradients (and of the column sums, which exist on this route only); without: one block per CU
+// (`grid_no_ws`) and 2*d atomics per block.
+struct LnBwdPlan {
+    int grid;
+    float* part;    // [grid][2][d] dgamma / dbeta block partials, or NULL: atomics
+    float* part3;   // [grid][d] column-sum block partials, or NULL
+};
+// false: a column sum was asked for and the workspace does not hold it
+bool ln_bwd_plan(LnBwdPlan& p, int units, int units_per_block, int grid_no_ws, int d, float* ws, long ws_floats,
+                 bool want_colsum) {
+    const int n_vec = want_colsum ? 3 : 2;
+    p = {grid_no_ws, nullptr, nullptr};
+    if (cx_ln_bwd_ws_holds(ws, ws_floats, n_vec, d)) {
+        const long cap = ws_floats / ((long)n_vec * d);
+        // 3 blocks per CU = the kernel's occupancy (130 VGPRs): one resident round, few partials; small inputs get at least 32
+        // rows per block (round 4: 8192 rows used to leave 768 partials of ~10 rows each, and the fold below -- 19 us for 768
+        // partials whatever the input -- was 4 % of a literal chunk_size-64 step)
+        p.grid = (units + units_per_block - 1) / units_per_block;
+        if (p.grid > 768) p.grid = 768;
+        if (p.grid > cap) p.grid = (int)cap;
+        p.part = ws;
+    }
+    if (want_colsum && !p.part) return false;
+    if (want_colsum) p.part3 = p.part + (size_t)p.grid * 2 * d;
+    return true;
+}
+int ln_bwd_finish(const LnBwdPlan& p, float* dgamma, float* dbeta, float* colsum, int d, void* stream) {
+    if (p.part && (dgamma || dbeta))
+        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * d + 63) / 64), dim3(256), 0, (hipStream_t)stream, p.part, dgamma,
+                           dbeta, p.grid, d);
+    if (colsum)
+        hipLaunchKernelGGL(colsum_reduce_kernel, dim3((d + 63) / 64), dim3(256), 0, (hipStream_t)stream, p.part3, colsum, p.grid, d);
+    return done();
+}
+
 // Shared launcher.  dz_colsum != NULL: fp32[d] += column sums of the dz written (needs the workspace: the sums go through
 // the deterministic two-stage reduction like dgamma / dbeta).
 int ln_bwd_launch(const uint16_t* dout_a, const uint16_t* dout_b, const uint16_t* z, const float* gamma, const float* mean,
@@ -930,36 +903,12 @@ int ln_bwd_launch(const uint16_t* dout_a, const uint16_t* dout_b, const uint16_t
     if (rows <= 0) return CX_OK;
     if (!dout_a || !z || !gamma || !mean || !rstd || !dz) return CX_ERR_ARG;
     const size_t smem = (size_t)8 * d * sizeof(float);
-    // with a workspace: many blocks (bandwidth) + deterministic two-stage parameter-gradient reduction;
-    // without: one block per CU and 2*d atomics per block
-    int grid = ln_grid_bwd(rows);
-    float* part = nullptr;
-    const long per_block = (dz_colsum ? 3L : 2L) * d;
-    if (ws && ws_floats >= per_block * 256) {
-        long cap = ws_floats / per_block;
-        // 3 blocks per CU = the kernel's occupancy (130 VGPRs): one resident round, few partials; small inputs get at least 32
-        // rows per block (round 4: 8192 rows used to leave 768 partials of ~10 rows each, and the fold below -- 19 us for 768
-        // partials whatever the input -- was 4 % of a literal chunk_size-64 step)
-        grid = (rows + 31) / 32;
-        if (grid > 768) grid = 768;
-        if (grid > cap) grid = (int)cap;
-        part = ws;
-    }
-    if (dz_colsum && !part) return CX_ERR_ARG;
-    float* part3 = dz_colsum ? part + (size_t)grid * 2 * d : nullptr;
-    if (dz_colsum) {
-        CX_LN_DISPATCH(d, hipLaunchKernelGGL((ln_bwd_kernel<NCH, true>), dim3(grid), dim3(256), smem, (hipStream_t)stream, dout_a,
-                                             dout_b, z, gamma, mean, rstd, dz_extra, dz, dgamma, dbeta, part, part3, rows));
-    } else {
-        CX_LN_DISPATCH(d, hipLaunchKernelGGL((ln_bwd_kernel<NCH, false>), dim3(grid), dim3(256), smem, (hipStream_t)stream, dout_a,
-                                             dout_b, z, gamma, mean, rstd, dz_extra, dz, dgamma, dbeta, part, part3, rows));
-    }
-    if (part && (dgamma || dbeta))
-        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * d + 63) / 64), dim3(256), 0, (hipStream_t)stream, part,
-                           dgamma, dbeta, grid, d);
-    if (dz_colsum)
-        hipLaunchKernelGGL(colsum_reduce_kernel, dim3((d + 63) / 64), dim3(256), 0, (hipStream_t)stream, part3, dz_colsum, grid, d);
-    return done();
+    LnBwdPlan p;
+    if (!ln_bwd_plan(p, rows, 32, ln_grid_bwd(rows), d, ws, ws_floats, dz_colsum)) return CX_ERR_ARG;
+    CX_LN_DISPATCH_CS(d, dz_colsum, hipLaunchKernelGGL((ln_bwd_kernel<NCH, CS>), dim3(p.grid), dim3(256), smem, (hipStream_t)stream,
+                                                       dout_a, dout_b, z, gamma, mean, rstd, dz_extra, dz, dgamma, dbeta, p.part,
+                                                       p.part3, rows));
+    return ln_bwd_finish(p, dgamma, dbeta, dz_colsum, d, stream);
 }
 }  // namespace
 
@@ -982,32 +931,12 @@ int cx_layernorm_bwd_pooled(const float* demb, const float* emb, const float* no
     if (rows <= 0 || B <= 0) return CX_OK;
     if (!demb || !emb || !norm || !cu_seqlens || !z || !gamma || !mean || !rstd || !dz) return CX_ERR_ARG;
     const size_t smem = ((size_t)8 * d + 8) * sizeof(float);
-    int grid = B < 256 ? B : 256;
-    float* part = nullptr;
-    const long per_block = (dz_colsum ? 3L : 2L) * d;
-    if (ws && ws_floats >= per_block * 256) {
-        const long cap = ws_floats / per_block;
-        grid = B < 768 ? B : 768;
-        if (grid > cap) grid = (int)cap;
-        part = ws;
-    }
-    if (dz_colsum && !part) return CX_ERR_ARG;
-    float* part3 = dz_colsum ? part + (size_t)grid * 2 * d : nullptr;
-    if (dz_colsum) {
-        CX_LN_DISPATCH(d, hipLaunchKernelGGL((ln_bwd_pooled_kernel<NCH, true>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
-                                             demb, emb, norm, cu_seqlens, B, pool_mode, normalize, z, gamma, mean, rstd, dz, dgamma,
-                                             dbeta, part, part3));
-    } else {
-        CX_LN_DISPATCH(d, hipLaunchKernelGGL((ln_bwd_pooled_kernel<NCH, false>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
-                                             demb, emb, norm, cu_seqlens, B, pool_mode, normalize, z, gamma, mean, rstd, dz, dgamma,
-                                             dbeta, part, part3));
-    }
-    if (part && (dgamma || dbeta))
-        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * d + 63) / 64), dim3(256), 0, (hipStream_t)stream, part,
-                           dgamma, dbeta, grid, d);
-    if (dz_colsum)
-        hipLaunchKernelGGL(colsum_reduce_kernel, dim3((d + 63) / 64), dim3(256), 0, (hipStream_t)stream, part3, dz_colsum, grid, d);
-    return done();
+    LnBwdPlan p;
+    if (!ln_bwd_plan(p, B, 1, B < 256 ? B : 256, d, ws, ws_floats, dz_colsum)) return CX_ERR_ARG;
+    CX_LN_DISPATCH_CS(d, dz_colsum, hipLaunchKernelGGL((ln_bwd_pooled_kernel<NCH, CS>), dim3(p.grid), dim3(256), smem,
+                                                       (hipStream_t)stream, demb, emb, norm, cu_seqlens, B, pool_mode, normalize, z,
+                                                       gamma, mean, rstd, dz, dgamma, dbeta, p.part, p.part3));
+    return ln_bwd_finish(p, dgamma, dbeta, dz_colsum, d, stream);
 }
 
 int cx_dropout_add_layernorm_fwd(const uint16_t* x0, const uint16_t* residual, const float* gamma, const float* beta,
@@ -1031,7 +960,7 @@ int cx_dropout_add_layernorm_bwd(const uint16_t* dout_a, const uint16_t* dout_b,
 }
 
 // The same with dx0_colsum (may be NULL): fp32[d] += column sums of the bf16 dx0 written = the bias gradient of the Linear whose (dropped)
-// output the LayerNorm consumed; needs the workspace (>= 3 * d * 256 floats), CX_ERR_ARG without it.
+// output the LayerNorm consumed; needs the workspace to hold three partial vectors (ln_workspace.h), CX_ERR_ARG without it.
 int cx_dropout_add_layernorm_bwd_colsum(const uint16_t* dout_a, const uint16_t* dout_b, const uint16_t* z, const float* gamma,
                                         const float* mean, const float* rstd, uint16_t* dz, uint16_t* dx0, float* dgamma, float* dbeta,
                                         float* dx0_colsum, float* ws, long ws_floats, int rows, int d, float p, unsigned long long seed,
@@ -1041,31 +970,12 @@ int cx_dropout_add_layernorm_bwd_colsum(const uint16_t* dout_a, const uint16_t* 
     if (!(p > 0.f) || p >= 1.f) return CX_ERR_ARG;
     const CxDropout dr{p, seed, offset};
     const size_t smem = (size_t)8 * d * sizeof(float);
-    int grid = ln_grid_bwd(rows);
-    float* part = nullptr;
-    const long per_block = (dx0_colsum ? 3L : 2L) * d;
-    if (ws && ws_floats >= per_block * 256) {
-        long cap = ws_floats / per_block;
-        grid = (rows + 31) / 32;   // (as in ln_bwd_launch)
-        if (grid > 768) grid = 768;
-        if (grid > cap) grid = (int)cap;
-        part = ws;
-    }
-    if (dx0_colsum && !part) return CX_ERR_ARG;
-    float* part3 = dx0_colsum ? part + (size_t)grid * 2 * d : nullptr;
-    if (dx0_colsum) {
-        CX_LN_DISPATCH(d, hipLaunchKernelGGL((ln_bwd_drop_kernel<NCH, true>), dim3(grid), dim3(256), smem, (hipStream_t)stream, dout_a,
-                                             dout_b, z, gamma, mean, rstd, dz, dx0, dgamma, dbeta, part, part3, rows, dr, site));
-    } else {
-        CX_LN_DISPATCH(d, hipLaunchKernelGGL((ln_bwd_drop_kernel<NCH, false>), dim3(grid), dim3(256), smem, (hipStream_t)stream, dout_a,
-                                             dout_b, z, gamma, mean, rstd, dz, dx0, dgamma, dbeta, part, part3, rows, dr, site));
-    }
-    if (part && (dgamma || dbeta))
-        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * d + 63) / 64), dim3(256), 0, (hipStream_t)stream, part, dgamma, dbeta,
-                           grid, d);
-    if (dx0_colsum)
-        hipLaunchKernelGGL(colsum_reduce_kernel, dim3((d + 63) / 64), dim3(256), 0, (hipStream_t)stream, part3, dx0_colsum, grid, d);
-    return done();
+    LnBwdPlan pl;
+    if (!ln_bwd_plan(pl, rows, 32, ln_grid_bwd(rows), d, ws, ws_floats, dx0_colsum)) return CX_ERR_ARG;
+    CX_LN_DISPATCH_CS(d, dx0_colsum, hipLaunchKernelGGL((ln_bwd_drop_kernel<NCH, CS>), dim3(pl.grid), dim3(256), smem,
+                                                        (hipStream_t)stream, dout_a, dout_b, z, gamma, mean, rstd, dz, dx0, dgamma,
+                                                        dbeta, pl.part, pl.part3, rows, dr, site));
+    return ln_bwd_finish(pl, dgamma, dbeta, dx0_colsum, d, stream);
 }
 
 int cx_dropout_scale(uint16_t* x, long n, float p, unsigned long long seed, unsigned long long offset, unsigned int site,

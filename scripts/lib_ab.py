@@ -1,9 +1,16 @@
-"""Same-box A/B of whole LIBRARIES (the product .so against variants built by scripts/build_variant.py) on isolated launches of
-the step's kernels: every library is loaded side by side (ctypes), rounds are interleaved (lib A, lib B, ..., lib A, ...) so that
-clock / power drift of the box hits all of them alike, and every variant's output is compared with the base library's (bit-identical
-or the max relative difference).  usage:
+"""Same-box A/B of whole LIBRARIES (the product .so against variants built by scripts/build_variant.py, or any other build of
+the library given by path) on isolated launches of the step's kernels: every library is loaded side by side (ctypes), rounds are
+interleaved (lib A, lib B, ..., lib A, ...) so that clock / power drift of the box hits all of them alike, and every library's
+output is compared with the first library's (bit-identical or the max relative difference).  usage:
     python scripts/lib_ab.py [--libs base,hi1,hi2] [--cases swiglu_bwd,attn_bwd] [--chunk 2048] [--rounds 7] [--reps 6]
-`base` = contrastors_amd/lib/libcontrastors_hip.so; any other name N = contrastors_amd/lib/variants/libcontrastors_hip_N.so."""
+    python scripts/lib_ab.py --libs /path/to/parent.so,/path/to/parent_copy.so,base --cases ln_fwd,ln_bwd_ws [--width 768]
+`base` = contrastors_amd/lib/libcontrastors_hip.so; a name with a `/` is the path of a .so; any other name N =
+contrastors_amd/lib/variants/libcontrastors_hip_N.so.  Two copies of one build among the libraries give the yardstick for the
+others: the ratio between them, and the `spread` column (max - min over the median of the first library's per-round times), are
+what the box cannot tell from no change.  Operands are allocated only for the groups of cases selected (GEMM, attention, LayerNorm).
+The LayerNorm cases run at T = chunk * 128 rows of --width columns (the metric's 262144 x 768 by default) and report the bytes they
+must move as TB/s; each lists only its deterministic outputs (the atomically accumulated vectors are held to bounds by
+tests/test_layernorm_edges_gpu.py)."""
 import argparse
 import ctypes as C
 import sys
@@ -22,11 +29,12 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--reps", type=int, default=6)
 ap.add_argument("--seq", type=int, default=128)
 ap.add_argument("--rotary", type=int, default=1, help="0: no rotation tables (pre-rotated long sequences, image towers)")
+ap.add_argument("--width", type=int, default=768, help="LayerNorm cases: row width (256, 512, 768 or 1024)")
 a = ap.parse_args()
 
 
 def load(name):
-    path = _C.LIB_PATH if name == "base" else _C.LIB_PATH.parent / "variants" / f"libcontrastors_hip_{name}.so"
+    path = _C.LIB_PATH if name == "base" else Path(name) if "/" in name else _C.LIB_PATH.parent / "variants" / f"libcontrastors_hip_{name}.so"
     h = C.CDLL(str(path))
     for fn, (res, args) in _C._SIGS.items():
         if hasattr(h, fn):
@@ -36,78 +44,151 @@ def load(name):
 
 
 names = a.libs.split(",")
+labels = {n: Path(n).stem if "/" in n else n for n in names}
 libs = {n: load(n) for n in names}
 dev = "cuda"
 s = torch.cuda.current_stream().cuda_stream
 g = torch.Generator(device=dev).manual_seed(0)
 rn = lambda *sh, std=1.0: (torch.randn(*sh, device=dev, generator=g) * std).bfloat16()   # noqa: E731
+rf = lambda *sh, std=1.0: torch.randn(*sh, device=dev, generator=g) * std   # noqa: E731
 P = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+E = lambda *sh, dt=torch.bfloat16: torch.empty(*sh, device=dev, dtype=dt)   # noqa: E731
 T, d, I, H, S = a.chunk * 128, 768, 3072, 12, a.seq
-x, res = rn(T, d), rn(T, d)
-w1, w2t, w2, wo, wqkv = rn(2 * I, d, std=0.05), rn(I, d, std=0.05), rn(d, I, std=0.05), rn(d, d, std=0.05), rn(3 * d, d, std=0.05)
-act, gate = rn(T, I), rn(T, I, std=2.0)
-x3, wqkv_t = rn(T, 3 * d), rn(d, 3 * d, std=0.05)
-x6, w1_t = rn(T, 2 * I), rn(d, 2 * I, std=0.05)
-dyg = torch.empty(T, 2 * I, device=dev, dtype=torch.bfloat16)
-out_d = torch.empty(T, d, device=dev, dtype=torch.bfloat16)
-out_3d = torch.empty(T, 3 * d, device=dev, dtype=torch.bfloat16)
-out_I = torch.empty(T, I, device=dev, dtype=torch.bfloat16)
-gs = torch.empty(T, I, device=dev, dtype=torch.bfloat16)
-# attention (S <= 128 single-pass kernels at S = 128; ragged: lengths 64..128)
-B = T // S
-qkv = rn(T, 3 * H * 64, std=0.5)
-cu = torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=dev)
-inv = 1.0 / (1000.0 ** (torch.arange(0, 64, 2, dtype=torch.float32) / 64))
-fr = torch.outer(torch.arange(max(S, 128), dtype=torch.float32), inv)
-cos, sin = torch.cos(fr).to(dev).contiguous(), torch.sin(fr).to(dev).contiguous()
-if not a.rotary:
-    cos = sin = None
-att_out = torch.empty(T, H * 64, device=dev, dtype=torch.bfloat16)
-lse = torch.empty(H * T, device=dev)
-dout = rn(T, H * 64)
-dqkv = torch.empty_like(qkv)
-delta = torch.empty(H * T, device=dev)
-lens = torch.randint(S // 2, S + 1, (B,), generator=torch.Generator().manual_seed(1))
-cu_r = torch.zeros(B + 1, dtype=torch.int32)
-cu_r[1:] = lens.cumsum(0)
-cu_r = cu_r.to(dev)
-T_r = int(lens.sum())
 
-# name -> (flop, outputs to compare, call(lib))
-cases = {
-    "swiglu_bwd": (2.0 * T * I * d, [dyg], lambda L: L.cx_gemm_bf16_swiglu_bwd_gate(P(x), P(w2t), P(act), P(gate), P(dyg), T, I, d, d, d, I, 2 * I, s)),
-    "swiglu_fwd_save": (2.0 * T * 2 * I * d, [gs, out_I], lambda L: L.cx_gemm_bf16_swiglu_gate(P(x), P(w1), P(gs), P(out_I), T, I, d, d, d, I, I, s)),
-    "swiglu_fwd": (2.0 * T * 2 * I * d, [out_I], lambda L: L.cx_gemm_bf16_swiglu_gate(P(x), P(w1), None, P(out_I), T, I, d, d, d, I, I, s)),
-    "qkv_fwd": (2.0 * T * 3 * d * d, [out_3d], lambda L: L.cx_gemm_bf16_nt(P(x), P(wqkv), P(out_3d), None, T, 3 * d, d, d, d, 3 * d, 0, 1, 1.0, s)),
-    "out_dgrad": (2.0 * T * d * d, [out_d], lambda L: L.cx_gemm_bf16_nt(P(x), P(wo), P(out_d), None, T, d, d, d, d, d, 0, 1, 1.0, s)),
-    "out_fwd_res": (2.0 * T * d * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(x), P(wo), P(out_d), None, P(res), T, d, d, d, d, d, d, s)),
-    "fc2_fwd_res": (2.0 * T * I * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(act), P(w2), P(out_d), None, P(res), T, d, I, I, I, d, d, s)),
-    "qkv_dgrad_res": (2.0 * T * 3 * d * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(x3), P(wqkv_t), P(out_d), None, P(res), T, d, 3 * d, 3 * d, 3 * d, d, d, s)),
-    "fc1_dgrad_res": (2.0 * T * 2 * I * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(x6), P(w1_t), P(out_d), None, P(res), T, d, 2 * I, 2 * I, 2 * I, d, d, s)),
-    "attn_fwd": (4.0 * S * S * 64 * B * H, [att_out, lse], lambda L: L.cx_attn_varlen_fwd(P(qkv), P(cu), P(cos), P(sin), P(att_out), P(lse), B, H, T, S, 0.125, s)),
-    "attn_bwd": (10.0 * S * S * 64 * B * H, [dqkv], lambda L: L.cx_attn_varlen_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu), P(cos), P(sin), P(delta), P(dqkv), B, H, T, S, 0.125, s)),
-    # (A/B of CX_ATTN_DELTA_IN builds: `delta` is filled beforehand by the base library's general kernels, see below)
-    "attn_bwd_dpre": (10.0 * S * S * 64 * B * H, [dqkv], lambda L: L.cx_attn_varlen_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu), P(cos), P(sin), P(delta), P(dqkv), B, H, T, S, 0.125, s)),
-    "attn_bwd_drop": (10.0 * S * S * 64 * B * H, [dqkv], lambda L: L.cx_attn_varlen_dropout_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu), P(cos), P(sin), P(delta), P(dqkv), B, H, T, S, 0.125, 0.1, 1234, 0, 0, s)),
-    "attn_fwd_drop": (4.0 * S * S * 64 * B * H, [att_out, lse], lambda L: L.cx_attn_varlen_dropout_fwd(P(qkv), P(cu), P(cos), P(sin), P(att_out), P(lse), B, H, T, S, 0.125, 0.1, 1234, 0, 0, s)),
-    "attn_bwd_ragged": (0.0, [dqkv], lambda L: L.cx_attn_varlen_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu_r), P(cos), P(sin), P(delta), P(dqkv), B, H, T_r, S, 0.125, s)),
-}
-want = [c for c in a.cases.split(",") if c] or list(cases)
-print(f"# T = {T} token rows, seq {S}; median of {a.rounds} interleaved rounds x {a.reps} launches (us); libs: {names}")
-hdr = f"{'case':18s}" + "".join(f"{n + ' us':>12s}{'TF':>8s}" for n in names) + "".join(f"{n + '/base':>12s}{'maxrel':>10s}" for n in names[1:])
-print(hdr)
-for cname in want:
-    fl, outs, call = cases[cname]
-    if cname.startswith("attn_bwd"):   # its inputs: a forward of the base library on the same sequences
-        libs[names[0]].cx_attn_varlen_fwd(P(qkv), P(cu_r if cname.endswith("ragged") else cu), P(cos), P(sin), P(att_out), P(lse), B, H,
-                                           T_r if cname.endswith("ragged") else T, S, 0.125, s)
-    if cname == "attn_bwd_dpre":   # delta = rowsum(dO * O) into `delta` (H, T): the general (max_seqlen > 128) path computes it first
+
+# Every group: name -> (work, outputs to compare, call(lib)[, prep()]).  work = flop (GEMM, attention: the TF column) or bytes
+# (LayerNorm: TB/s); the outputs are zeroed, then prep() (if any) restores what the call overwrites, before each compared call.
+def gemm_cases():
+    x, res = rn(T, d), rn(T, d)
+    w1, w2t, w2, wo, wqkv = rn(2 * I, d, std=0.05), rn(I, d, std=0.05), rn(d, I, std=0.05), rn(d, d, std=0.05), rn(3 * d, d, std=0.05)
+    act, gate = rn(T, I), rn(T, I, std=2.0)
+    x3, wqkv_t = rn(T, 3 * d), rn(d, 3 * d, std=0.05)
+    x6, w1_t = rn(T, 2 * I), rn(d, 2 * I, std=0.05)
+    dyg, out_d, out_3d, out_I, gs = E(T, 2 * I), E(T, d), E(T, 3 * d), E(T, I), E(T, I)
+    return {
+        "swiglu_bwd": (2.0 * T * I * d, [dyg], lambda L: L.cx_gemm_bf16_swiglu_bwd_gate(P(x), P(w2t), P(act), P(gate), P(dyg), T, I, d, d, d, I, 2 * I, s)),
+        "swiglu_fwd_save": (2.0 * T * 2 * I * d, [gs, out_I], lambda L: L.cx_gemm_bf16_swiglu_gate(P(x), P(w1), P(gs), P(out_I), T, I, d, d, d, I, I, s)),
+        "swiglu_fwd": (2.0 * T * 2 * I * d, [out_I], lambda L: L.cx_gemm_bf16_swiglu_gate(P(x), P(w1), None, P(out_I), T, I, d, d, d, I, I, s)),
+        "qkv_fwd": (2.0 * T * 3 * d * d, [out_3d], lambda L: L.cx_gemm_bf16_nt(P(x), P(wqkv), P(out_3d), None, T, 3 * d, d, d, d, 3 * d, 0, 1, 1.0, s)),
+        "out_dgrad": (2.0 * T * d * d, [out_d], lambda L: L.cx_gemm_bf16_nt(P(x), P(wo), P(out_d), None, T, d, d, d, d, d, 0, 1, 1.0, s)),
+        "out_fwd_res": (2.0 * T * d * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(x), P(wo), P(out_d), None, P(res), T, d, d, d, d, d, d, s)),
+        "fc2_fwd_res": (2.0 * T * I * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(act), P(w2), P(out_d), None, P(res), T, d, I, I, I, d, d, s)),
+        "qkv_dgrad_res": (2.0 * T * 3 * d * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(x3), P(wqkv_t), P(out_d), None, P(res), T, d, 3 * d, 3 * d, 3 * d, d, d, s)),
+        "fc1_dgrad_res": (2.0 * T * 2 * I * d, [out_d], lambda L: L.cx_gemm_bf16_nt_residual(P(x6), P(w1_t), P(out_d), None, P(res), T, d, 2 * I, 2 * I, 2 * I, d, d, s)),
+    }
+
+
+def attn_cases():
+    # attention (S <= 128 single-pass kernels at S = 128; ragged: lengths 64..128)
+    B = T // S
+    qkv = rn(T, 3 * H * 64, std=0.5)
+    cu = torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=dev)
+    inv = 1.0 / (1000.0 ** (torch.arange(0, 64, 2, dtype=torch.float32) / 64))
+    fr = torch.outer(torch.arange(max(S, 128), dtype=torch.float32), inv)
+    cos, sin = torch.cos(fr).to(dev).contiguous(), torch.sin(fr).to(dev).contiguous()
+    if not a.rotary:
+        cos = sin = None
+    att_out, lse, dout = E(T, H * 64), E(H * T, dt=torch.float32), rn(T, H * 64)
+    dqkv, delta = torch.empty_like(qkv), E(H * T, dt=torch.float32)
+    lens = torch.randint(S // 2, S + 1, (B,), generator=torch.Generator().manual_seed(1))
+    cu_r = torch.zeros(B + 1, dtype=torch.int32)
+    cu_r[1:] = lens.cumsum(0)
+    cu_r = cu_r.to(dev)
+    T_r = int(lens.sum())
+
+    def fwd_first(ragged):   # the inputs of a backward: a forward of the first library on the same sequences
+        return lambda: libs[names[0]].cx_attn_varlen_fwd(P(qkv), P(cu_r if ragged else cu), P(cos), P(sin), P(att_out), P(lse), B, H,
+                                                         T_r if ragged else T, S, 0.125, s)
+
+    def delta_first():   # delta = rowsum(dO * O) into `delta` (H, T): the general (max_seqlen > 128) path computes it first
+        fwd_first(False)()
         assert libs[names[0]].cx_attn_varlen_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu), P(cos), P(sin), P(delta), P(dqkv), B, H, T, S + 1, 0.125, s) == 0
         torch.cuda.synchronize()
+
+    bwd = lambda L: L.cx_attn_varlen_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu), P(cos), P(sin), P(delta), P(dqkv), B, H, T, S, 0.125, s)   # noqa: E731
+    return {
+        "attn_fwd": (4.0 * S * S * 64 * B * H, [att_out, lse], lambda L: L.cx_attn_varlen_fwd(P(qkv), P(cu), P(cos), P(sin), P(att_out), P(lse), B, H, T, S, 0.125, s)),
+        "attn_bwd": (10.0 * S * S * 64 * B * H, [dqkv], bwd, None, fwd_first(False)),
+        # (A/B of CX_ATTN_DELTA_IN builds: `delta` is filled beforehand by the first library's general kernels)
+        "attn_bwd_dpre": (10.0 * S * S * 64 * B * H, [dqkv], bwd, None, delta_first),
+        "attn_bwd_drop": (10.0 * S * S * 64 * B * H, [dqkv], lambda L: L.cx_attn_varlen_dropout_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu), P(cos), P(sin), P(delta), P(dqkv), B, H, T, S, 0.125, 0.1, 1234, 0, 0, s), None, fwd_first(False)),
+        "attn_fwd_drop": (4.0 * S * S * 64 * B * H, [att_out, lse], lambda L: L.cx_attn_varlen_dropout_fwd(P(qkv), P(cu), P(cos), P(sin), P(att_out), P(lse), B, H, T, S, 0.125, 0.1, 1234, 0, 0, s)),
+        "attn_bwd_ragged": (0.0, [dqkv], lambda L: L.cx_attn_varlen_bwd(P(dout), P(qkv), P(att_out), P(lse), P(cu_r), P(cos), P(sin), P(delta), P(dqkv), B, H, T_r, S, 0.125, s), None, fwd_first(True)),
+    }
+
+
+def ln_cases():
+    w = a.width
+    f32 = torch.float32
+    x, r, dout = rn(T, w), rn(T, w), rn(T, w)
+    gam, bet = 1 + rf(w, std=0.1), rf(w, std=0.1)
+    out, z, dz, dx0 = E(T, w), E(T, w), E(T, w), E(T, w)
+    mean_o, rstd_o, mean, rstd = E(T, dt=f32), E(T, dt=f32), E(T, dt=f32), E(T, dt=f32)
+    dg, db, cs = E(w, dt=f32), E(w, dt=f32), E(w, dt=f32)
+    ws = E(3 * w * 768, dt=f32)
+    # the backward cases take x as the stored z, with the first library's statistics of it
+    assert libs[names[0]].cx_layernorm_fwd(P(x), None, P(gam), P(bet), P(out), None, P(mean), P(rstd), T, w, 1e-12, s) == 0
+    Bq = T // 128                                         # pooled: sequences of 128 rows
+    demb, emb, norm = rf(Bq, w), torch.nn.functional.normalize(rf(Bq, w), dim=-1), 0.5 + torch.rand(Bq, device=dev, generator=g)
+    cu = torch.arange(0, (Bq + 1) * 128, 128, dtype=torch.int32, device=dev)
+    xf, rf_, doutf = x.float(), r.float(), dout.float()   # mixed kernels, every operand fp32
+    outf, zf = E(T, w, dt=f32), E(T, w, dt=f32)
+    ALL_F32 = 1 | 2 | 4 | 8
+    vocab = 30528                                         # embedding: every slot a token, positions 0 .. 127
+    ids = torch.randint(0, vocab, (Bq, 128), device=dev, generator=g)
+    idx = torch.arange(T, dtype=torch.int32, device=dev)
+    word, type_e, pos_e = rf(vocab, w, std=0.5), rf(2, w, std=0.5), rf(128, w, std=0.5)
+    sids, perm = torch.sort(ids.flatten().to(torch.int32), stable=True)
+    perm = perm.to(torch.int32)
+    dword, scratch, dt0, dpos = E(vocab, w, dt=f32), E(T, w, dt=f32), torch.zeros(w, device=dev), torch.zeros(128, w, device=dev)
+    inplace = E(T, w)
+    Bt, n_ws = 2.0 * T * w, ws.numel()                    # bytes of one bf16 (T, w) operand
+    DROP = (0.1, 1234, 0, 3)
+    return {
+        "ln_fwd": (2 * Bt, [out, mean_o, rstd_o], lambda L: L.cx_layernorm_fwd(P(x), None, P(gam), P(bet), P(out), None, P(mean_o), P(rstd_o), T, w, 1e-12, s)),
+        "ln_fwd_res_z": (4 * Bt, [out, z, mean_o, rstd_o], lambda L: L.cx_layernorm_fwd(P(x), P(r), P(gam), P(bet), P(out), P(z), P(mean_o), P(rstd_o), T, w, 1e-12, s)),
+        "ln_bwd_ws": (3 * Bt, [dz, dg, db], lambda L: L.cx_layernorm_bwd(P(dout), None, P(x), P(gam), P(mean), P(rstd), None, P(dz), P(dg), P(db), P(ws), n_ws, T, w, s)),
+        "ln_bwd_colsum_ws": (3 * Bt, [dz, dg, db, cs], lambda L: L.cx_layernorm_bwd_colsum(P(dout), None, P(x), P(gam), P(mean), P(rstd), None, P(dz), P(dg), P(db), P(cs), P(ws), n_ws, T, w, s)),
+        "ln_bwd_atomics": (3 * Bt, [dz], lambda L: L.cx_layernorm_bwd(P(dout), None, P(x), P(gam), P(mean), P(rstd), None, P(dz), P(dg), P(db), None, 0, T, w, s)),
+        "ln_pooled_ws": (2 * Bt, [dz, dg, db, cs], lambda L: L.cx_layernorm_bwd_pooled(P(demb), P(emb), P(norm), P(cu), Bq, 0, 1, P(x), P(gam), P(mean), P(rstd), P(dz), P(dg), P(db), P(cs), P(ws), n_ws, T, w, s)),
+        "ln_drop_fwd": (4 * Bt, [out, z, mean_o, rstd_o], lambda L: L.cx_dropout_add_layernorm_fwd(P(x), P(r), P(gam), P(bet), P(out), P(z), P(mean_o), P(rstd_o), T, w, 1e-12, *DROP, s)),
+        "ln_drop_bwd_colsum_ws": (4 * Bt, [dz, dx0, dg, db, cs], lambda L: L.cx_dropout_add_layernorm_bwd_colsum(P(dout), None, P(x), P(gam), P(mean), P(rstd), P(dz), P(dx0), P(dg), P(db), P(cs), P(ws), n_ws, T, w, *DROP, s)),
+        "ln_mixed_fwd_f32": (8 * Bt, [outf, zf, mean_o, rstd_o], lambda L: L.cx_layernorm_fwd_mixed(P(xf), P(rf_), P(gam), P(bet), P(outf), P(zf), P(mean_o), P(rstd_o), T, w, 1e-12, ALL_F32, s)),
+        "ln_mixed_bwd_f32": (8 * Bt, [outf, zf], lambda L: L.cx_layernorm_bwd_mixed(P(doutf), P(xf), P(gam), P(mean), P(rstd), None, P(outf), P(zf), P(dg), P(db), T, w, ALL_F32, s)),
+        # word rows in fp32 (2 Bt) -> out; backward: dout + word rows -> fp32 row gradients (2 Bt), read back by the scatter
+        "embed_fwd": (3 * Bt, [out, mean_o, rstd_o], lambda L: L.cx_embed_ln_fwd(P(ids), P(idx), P(word), P(type_e), P(pos_e), P(gam), P(bet), P(out), P(mean_o), P(rstd_o), T, 128, w, 1e-12, s)),
+        "embed_bwd_sorted": (7 * Bt, [scratch, dword], lambda L: L.cx_embed_ln_bwd_sorted(P(dout), None, P(ids), P(idx), P(word), P(type_e), P(pos_e), P(gam), P(mean), P(rstd), P(dword), P(dt0), P(dpos), P(dg), P(db), T, 128, w, 0, vocab, P(sids), P(perm), P(scratch), s)),
+        "dropout_scale": (2 * Bt, [inplace], lambda L: L.cx_dropout_scale(P(inplace), T * w, *DROP, s), lambda: inplace.copy_(x)),
+    }
+
+
+GROUPS = {gemm_cases: ("swiglu_bwd", "swiglu_fwd_save", "swiglu_fwd", "qkv_fwd", "out_dgrad", "out_fwd_res", "fc2_fwd_res", "qkv_dgrad_res", "fc1_dgrad_res"),
+          attn_cases: ("attn_fwd", "attn_bwd", "attn_bwd_dpre", "attn_bwd_drop", "attn_fwd_drop", "attn_bwd_ragged"),
+          ln_cases: ("ln_fwd", "ln_fwd_res_z", "ln_bwd_ws", "ln_bwd_colsum_ws", "ln_bwd_atomics", "ln_pooled_ws", "ln_drop_fwd", "ln_drop_bwd_colsum_ws",
+                     "ln_mixed_fwd_f32", "ln_mixed_bwd_f32", "embed_fwd", "embed_bwd_sorted", "dropout_scale")}
+want = [c for c in a.cases.split(",") if c] or [c for grp in GROUPS.values() for c in grp]
+unknown = [c for c in want if not any(c in grp for grp in GROUPS.values())]
+assert not unknown, f"unknown cases {unknown}"
+cases = {}
+for build, grp in GROUPS.items():
+    if any(c in grp for c in want):
+        cases.update(build())
+first = names[0]
+print(f"# T = {T} token rows, seq {S}, LayerNorm width {a.width}; median of {a.rounds} interleaved rounds x {a.reps} launches (us); "
+      f"libs: {[labels[n] for n in names]}")
+hdr = f"{'case':22s}" + "".join(f"{labels[n] + ' us':>14s}{'T/s':>8s}" for n in names) + f"{'spread':>8s}"
+hdr += "".join(f"{labels[n] + '/' + labels[first]:>22s}{'maxrel':>10s}" for n in names[1:])
+print(hdr)
+for cname in want:
+    fl, outs, call, prep, once = (cases[cname] + (None, None))[:5]
+    if once:
+        once()
     ref, diffs = None, {}
     for n in names:
         for o in outs:
             o.zero_()
+        if prep:
+            prep()
         rc = call(libs[n])
         assert rc == 0, (cname, n, rc)
         torch.cuda.synchronize()
@@ -115,7 +196,7 @@ for cname in want:
         if ref is None:
             ref = got
         else:
-            same = all(torch.equal(x_, y_) for x_, y_ in zip(got, ref))
+            same = all(torch.equal(x_.view(torch.uint8), y_.view(torch.uint8)) for x_, y_ in zip(got, ref))
             rel = max(float((x_.float() - y_.float()).norm() / (y_.float().norm() + 1e-30)) for x_, y_ in zip(got, ref))
             diffs[n] = "bit-ident" if same else f"{rel:.2e}"
     t = {n: [] for n in names}
@@ -129,6 +210,7 @@ for cname in want:
             torch.cuda.synchronize()
             t[n].append(e0.elapsed_time(e1) * 1e3 / a.reps)
     med = {n: sorted(v)[len(v) // 2] for n, v in t.items()}
-    row = f"{cname:18s}" + "".join(f"{med[n]:12.1f}{(fl / med[n] / 1e6 if fl else 0):8.1f}" for n in names)
-    row += "".join(f"{med[n] / med[names[0]]:12.3f}{diffs[n]:>10s}" for n in names[1:])
+    row = f"{cname:22s}" + "".join(f"{med[n]:14.1f}{(fl / med[n] / 1e6 if fl else 0):8.2f}" for n in names)
+    row += f"{(max(t[first]) - min(t[first])) / med[first]:8.3f}"
+    row += "".join(f"{med[n] / med[first]:22.3f}{diffs[n]:>10s}" for n in names[1:])
     print(row, flush=True)

@@ -37,6 +37,11 @@ C_MEAS = {
     "bwd_rms": {"dz": 820.0, "dgamma": 3.8, "dbeta": 3.0},
     "bwd_drop": {"dz": 115.0, "dx0": 115.0, "dgamma": 3.6, "dbeta": 0.5, "colsum": 1.0},
     "pooled": {"dz": 300.0, "dgamma": 6.2, "dbeta": 12.0, "colsum": 4.3},
+    # the embedding kernels: z = (word + pos) + type is an exact fp32 sum the host reproduces, so these are fwd_f32 / bwd on
+    # the embedding inputs; "scatter" = dtype0 / dpos / dword, sums of fp32 dz rows, against 2^-24 * sum of the rows' S
+    # (a vocabulary row with one token receives that token's dz row: "scatter" cannot be below "dz")
+    "embed_fwd": {"out": 1.8e4, "out_tight": 3.6, "mean": 3.6, "rstd": 2.9},
+    "embed_bwd": {"dz": 102.0, "dgamma": 0.77, "dbeta": 0.44, "scatter": 102.0},
 }
 C_FACTOR = 4.0
 
@@ -216,6 +221,76 @@ def pooled_inputs(lens, d, seed=400, eps=1e-12):
     z = (x0.float() + res.float()).to(torch.bfloat16)
     st = ln_fwd_ref(z, None, gamma, None, eps)
     return dict(cu=cu, demb=demb, emb=emb, norm=norm, z=z, gamma=gamma, mean=st.mean.float(), rstd=st.rstd.float(), T=T, B=B)
+
+
+def embed_inputs(T, d, vocab, seq=128, seed=500, planted=(), eps=1e-12):
+    """The operands of cx_embed_ln_fwd / _bwd(_sorted) on the CPU: ids (Bq, seq) int64 and indices int32[T] = the flat
+    positions of the unpadded tokens (sequence lengths 64 .. 128, so tokens of every position and a ragged batch), word
+    (vocab, d) / type (2, d) / pos (seq, d) in fp32 with the row profile of the other inputs on the word rows, gamma, beta,
+    dout_a / dout_b in bf16.  planted = ((id, count), ...): `count` tokens at seeded places carry `id`, the rest are
+    uniform over the vocabulary."""
+    lens, n = [], 0
+    while n < T:
+        lens.append(64 + (37 * len(lens)) % 65)
+        n += lens[-1]
+    indices = torch.cat([torch.arange(ln) + b * seq for b, ln in enumerate(lens)])[:T].to(torch.int32)
+    g = _gen(seed + d)
+    tok_ids = torch.randint(0, vocab, (T,), generator=g)
+    place = torch.randperm(T, generator=g)
+    at = 0
+    for tid, count in planted:
+        tok_ids[place[at:at + count]] = tid
+        at += count
+    assert at <= T
+    ids = torch.randint(0, vocab, (len(lens), seq), generator=g)          # padded slots hold ids nobody reads
+    ids.view(-1)[indices.long()] = tok_ids
+    gamma, beta = params(d)
+    e = dict(ids=ids, indices=indices, seq=seq, vocab=vocab, T=T, gamma=gamma, beta=beta,
+             word=rows_like(vocab, d, seed + d + 1, dtype=torch.float32),
+             pos=(0.5 * rows_like(seq, d, seed + d + 2, centred=True, dtype=torch.float32)),
+             type=0.1 * torch.randn(2, d, generator=g),
+             da=rows_like(T, d, seed + d + 3, centred=True, shift=2), db=rows_like(T, d, seed + d + 4, centred=True, shift=3))
+    return e
+
+
+# The shapes of the embedding edge tests (tests/test_layernorm_edges_gpu.py) and of the measurement of their constants.
+EMBED_FWD_SHAPES = tuple((77, d) for d in WIDTHS) + ((8197, 768),)   # 8197 > 2048 blocks x 4 waves: a wave's second row
+EMBED_PAD = 3
+
+
+def embed_fwd_inputs(T, d):
+    return embed_inputs(T, d, 512)
+
+
+def embed_bwd_inputs(d):
+    """T = 1029 > 256 blocks x 4 waves; 300 vocabulary rows, so the word-row atomics collide; the padding id occurs."""
+    return embed_inputs(1029, d, 300, seed=600, planted=((EMBED_PAD, 5),))
+
+
+def embed_sorted_inputs(d):
+    """T = 4101 > 1024 blocks x 4 waves; 8200 vocabulary rows > the scatter's 8192 blocks, with tokens on both rows of the
+    blocks that take two (v and v + 8192, v < 8); a row of 40 tokens and one of 9 (the fold, a wave summing several rows),
+    one of 3 (the fold with an idle wave), rows of one token (no fold) and -- T < vocabulary -- rows of none; the padding id
+    occurs."""
+    planted = ((EMBED_PAD, 6), (5, 40), (8195, 9), (7, 3)) + tuple((v, 1) for v in (0, 1, 2, 4, 6, 8192, 8193, 8194, 8196,
+                                                                                  8197, 8198, 8199))
+    return embed_inputs(4101, d, 8200, seed=700, planted=planted)
+
+
+def embed_z(word, type_e, pos_e, ids, indices, seq):
+    """z = (word[id] + pos[p]) + type[0] in fp32, the kernels' order (pos_e None: word[id] + type[0]): sums of two and three
+    fp32 values are correctly rounded on any device, so this IS the kernels' z.  Returns z, the token ids, the positions."""
+    tok = indices.long()
+    tid, p = ids.reshape(-1)[tok], tok % seq
+    z = word[tid]
+    if pos_e is not None:
+        z = z + pos_e[p]
+    return z + type_e[0], tid, p
+
+
+def scatter_rows(rows, index, n):
+    """out[index[t]] += rows[t] in the dtype of `rows` (fp64 for the references of dword / dpos)."""
+    return torch.zeros(n, rows.shape[1], dtype=rows.dtype, device=rows.device).index_add_(0, index, rows)
 
 
 # ---------------------------------------------------------------------------------------------------------- checker

@@ -1,6 +1,7 @@
 """The LayerNorm family of contrastors_amd/csrc/layernorm.hip against the fp64 reference of tests/ln_ref.py, per row, at the
 row counts where a wave takes a second and a third row, where each grid cap of the launchers binds, at all four widths, with
-every optional pointer NULL on its own, and through the C ABI for the mixed-dtype kernels.
+every optional pointer NULL on its own, and through the C ABI for the mixed-dtype kernels; the embedding kernels (gather +
+LayerNorm, its backward with the atomic and the sorted word-row reduction) at their grid caps.
 
 Every operand and result is a slice of a larger allocation whose 8 rows (8 elements for vectors) either side hold a NaN bit
 pattern: a read outside the slice poisons the result, a write outside it is found when the test ends (`_guards`).
@@ -14,6 +15,10 @@ and C_meas measured by tests/test_ln_ref_cpu.py on an fp32 emulation against the
     fwd_f32    3.7e6    5.0        3.9   5.5  | bwd_rms    820   -     3.8     3.0    -
     fwd_rms    5.6      -          -     3.2  | bwd_drop   115   115   3.6     0.5    1.0
     fwd_drop   9600     4.8        3.5   3.7  | pooled     300   -     6.2     12.0   4.3
+    embed_fwd  1.8e4    3.6        3.6   2.9  | embed_bwd  102   -     0.77    0.44   -      scatter 102
+
+(embed_bwd "scatter": dtype0, dpos and dword are sums of fp32 dz rows; each against the same sum of the fp64 dz rows under
+C 2^-24 sum|S_t| over the rows t it receives, S_t the scale of dz.)
 
 (`out` on S = |xhat g| + |b| alone is so large because S lacks the rounding of the row mean times rstd; ln_ref.check_out applies
 it together with `out_tight` on S + mean|z| rstd |g|, whichever is smaller.)  Each test reports its worst err / bound per entry
@@ -31,6 +36,10 @@ Which test reaches what (grid caps and branches of the launchers):
     pooled: B blocks / 256 cap, sequence loop wraps .................. test_pooled[...], test_pooled_sequence_loop_wraps[300]
     pooled: workspace, 768 cap, sequence loop wraps .................. test_pooled_sequence_loop_wraps[800]
     CX_LN_DISPATCH default ........................................... test_unsupported_width
+    embedding forward: ln_grid cap 2048, second row per wave ......... test_embed_fwd[8197-768]
+    embedding backward: ln_grid_bwd cap 256, every wave's second row . test_embed_bwd (1029 tokens)
+    sorted embedding backward: 1024-block cap; scatter: 8192-block cap,
+        no token / one token (no fold) / fold, += , padding row ...... test_embed_bwd_sorted (4101 tokens, 8200 rows)
 """
 import pytest
 import torch
@@ -492,6 +501,134 @@ def test_dropout_bwd(d, p):
             r["colsum"] = R.check_colsum("drop_bwd.colsum", cs.t, s["dx0"].t, C("bwd_drop", "colsum"))
         report("ln_edges.cx_dropout_add_layernorm_bwd" + ("_colsum" if colsum else ""), d=d, rows=rows, p=p, ws=ws_floats, **r)
         guards_ok()
+
+
+# ---------------------------------------------------------------------------------------------------------- embedding
+def embed_slabs(e, use_pos=True):
+    """The operands of the embedding kernels.  The integer operands are plain tensors, not slabs: a poisoned index would
+    not poison a result, it would send a read anywhere."""
+    s = dict(word=Slab(e["word"], name="word"), type=Slab(e["type"], name="type"), pos=Slab(e["pos"], name="pos") if use_pos else None,
+             g=Slab(e["gamma"], name="gamma"), b=Slab(e["beta"], name="beta"), ids=e["ids"].to(DEV), indices=e["indices"].to(DEV))
+    s["z"], s["tid"], s["p"] = R.embed_z(s["word"].t, s["type"].t, None if s["pos"] is None else s["pos"].t, s["ids"], s["indices"],
+                                         e["seq"])
+    return s
+
+
+@pytest.mark.parametrize("use_pos", [1, 0], ids=["pos", "nopos"])
+@pytest.mark.parametrize("T,d", R.EMBED_FWD_SHAPES)
+def test_embed_fwd(T, d, use_pos):
+    """77 tokens at every width, and 8197 tokens at d = 768: 2048 blocks x 4 waves take 8192, so a wave takes a second
+    token; with and without position embeddings."""
+    e = R.embed_fwd_inputs(T, d)
+    s = embed_slabs(e, use_pos)
+    out, mean, rstd = out_slab((T, d), BF, "out"), out_slab((T,), F32, "mean"), out_slab((T,), F32, "rstd")
+    _C.check(L().cx_embed_ln_fwd(s["ids"].data_ptr(), s["indices"].data_ptr(), s["word"].ptr, s["type"].ptr, P(s["pos"]), s["g"].ptr,
+                                 s["b"].ptr, out.ptr, mean.ptr, rstd.ptr, T, e["seq"], d, 1e-12, S()), "embed_ln_fwd")
+    f = R.ln_fwd_ref(s["z"], None, s["g"].t, s["b"].t, 1e-12)
+    report("ln_edges.cx_embed_ln_fwd", d=d, T=T, pos=use_pos, out=R.check_out("embed.out", out.t, f, "embed_fwd"),
+           mean=R.check_mean("embed.mean", mean.t, f, C("embed_fwd", "mean")),
+           rstd=R.check_rstd("embed.rstd", rstd.t, f, C("embed_fwd", "rstd")))
+
+
+def embed_bwd_operands(e, s, d, *, two, dpos, dword_fill=0.0):
+    """dout_a / dout_b, the statistics the forward would hand over (fp64 of the exact z, rounded to fp32), zeroed
+    accumulators, and the fp64 reference of dz."""
+    T = e["T"]
+    st = R.ln_fwd_ref(s["z"], None, s["g"].t, None, 1e-12)
+    o = dict(da=Slab(e["da"], name="dout_a"), db=Slab(e["db"], name="dout_b") if two else None,
+             mean=Slab(st.mean.float(), name="mean"), rstd=Slab(st.rstd.float(), name="rstd"),
+             dword=Slab(shape=(e["vocab"], d), dtype=F32, fill=dword_fill, name="dword"),
+             dtype0=Slab(shape=(d,), dtype=F32, fill=0.0, name="dtype0"),
+             dpos=Slab(shape=(e["seq"], d), dtype=F32, fill=0.0, name="dpos") if dpos else None,
+             dgamma=Slab(shape=(d,), dtype=F32, fill=0.0, name="dgamma"), dbeta=Slab(shape=(d,), dtype=F32, fill=0.0, name="dbeta"))
+    o["ref"] = R.ln_bwd_ref(o["da"].t, None if o["db"] is None else o["db"].t, s["z"], s["g"].t, o["mean"].t, o["rstd"].t, None)
+    o["args"] = (o["da"].ptr, P(o["db"]), s["ids"].data_ptr(), s["indices"].data_ptr(), s["word"].ptr, s["type"].ptr, P(s["pos"]),
+                 s["g"].ptr, o["mean"].ptr, o["rstd"].ptr, o["dword"].ptr, o["dtype0"].ptr, P(o["dpos"]), o["dgamma"].ptr,
+                 o["dbeta"].ptr, T, e["seq"], d, R.EMBED_PAD)
+    return o
+
+
+def check_embed_bwd(e, s, o, tag, dword_fill=0.0):
+    """dgamma / dbeta as everywhere; dtype0, dpos, dword against the scatter-added fp64 dz rows."""
+    ref, fam = o["ref"], "embed_bwd"
+    sc = lambda what, want, scale: R.check_rows(f"{tag}.{what}", o[what].t, want, cols_bound(fam, "scatter", scale))
+    r = dict(dgamma=R.check_rows(f"{tag}.dgamma", o["dgamma"].t, ref.dgamma, cols_bound(fam, "dgamma", ref.dgamma_abs)),
+             dbeta=R.check_rows(f"{tag}.dbeta", o["dbeta"].t, ref.dbeta, cols_bound(fam, "dbeta", ref.dbeta_abs)),
+             dtype0=sc("dtype0", ref.dz.sum(0), ref.scale.sum(0)))
+    if o["dpos"] is not None:
+        r["dpos"] = sc("dpos", R.scatter_rows(ref.dz, s["p"], e["seq"]), R.scatter_rows(ref.scale, s["p"], e["seq"]))
+    real = s["tid"] != R.EMBED_PAD
+    assert int((~real).sum()) > 0, "the padding id occurs"
+    want = R.scatter_rows(ref.dz[real], s["tid"][real], e["vocab"]) + dword_fill
+    r["dword"] = sc("dword", want, R.scatter_rows(ref.scale[real], s["tid"][real], e["vocab"]) + abs(dword_fill))
+    fill_bits = R.bits(torch.tensor([dword_fill], dtype=F32))[0].item()
+    assert bool((R.bits(o["dword"].t[R.EMBED_PAD]) == fill_bits).all()), "nn.Embedding(padding_idx): that row gets no gradient"
+    return r
+
+
+@pytest.mark.parametrize("d", WIDTHS)
+@pytest.mark.parametrize("null", ["none", "dout_b", "dpos", "pos_emb"])
+def test_embed_bwd(d, null):
+    """1029 tokens on 256 blocks x 4 waves: every wave takes a second token and five take a third; the word rows by fp32
+    atomics (300 rows: they collide).  NULL one at a time: dout_b, dpos (with positions in z), pos_emb (and with it dpos)."""
+    e = R.embed_bwd_inputs(d)
+    s = embed_slabs(e, use_pos=null != "pos_emb")
+    o = embed_bwd_operands(e, s, d, two=null != "dout_b", dpos=null not in ("dpos", "pos_emb"))
+    _C.check(L().cx_embed_ln_bwd(*o["args"], S()), "embed_ln_bwd")
+    report("ln_edges.cx_embed_ln_bwd", d=d, T=e["T"], null=null, **check_embed_bwd(e, s, o, "embed_bwd"))
+
+
+def sorted_scatter_of(dz, tid, fill, vocab):
+    """embed_scatter_sorted_kernel's sum on the host, in its order, from the fp32 rows it read: wave w adds the rows of its
+    vocabulary row's tokens w, w + 4, ... (token order) to 0, the four sums fold as ((w0 + w1) + w2) + w3, and the row adds
+    that once.  fp32 adds are correctly rounded everywhere: bit-exact."""
+    dz, tid = dz.cpu(), tid.cpu()
+    want = torch.full((vocab, dz.shape[1]), fill, dtype=F32)
+    order = torch.sort(tid, stable=True).indices
+    counts = torch.bincount(tid, minlength=vocab).tolist()
+    at = 0
+    for v, n in enumerate(counts):
+        toks = order[at:at + n]
+        at += n
+        if n == 0 or v == R.EMBED_PAD:
+            continue
+        waves = []
+        for w in range(4):
+            acc = torch.zeros(dz.shape[1], dtype=F32)
+            for t in toks[w::4].tolist():
+                acc = acc + dz[t]
+            waves.append(acc)
+        want[v] += waves[0] if n <= 1 else ((waves[0] + waves[1]) + waves[2]) + waves[3]
+    return want, counts
+
+
+@pytest.mark.parametrize("d", [256, 768])
+def test_embed_bwd_sorted(d):
+    """4101 tokens on 1024 blocks x 4 waves (a wave's second token), 8200 vocabulary rows on the scatter's 8192 blocks (the
+    first 8 take two rows, both with tokens), rows of 0 / 1 / 3 / 9 / 40 tokens, the padding id present, dword pre-filled:
+    the fp32 row gradients in the scratch against fp64, dword against the fp64 scatter AND bit for bit against the
+    kernel's own order of summation, and bit-identical from run to run."""
+    e = R.embed_sorted_inputs(d)
+    s = embed_slabs(e)
+    T, V, fill = e["T"], e["vocab"], 1.0
+    sids, perm = torch.sort(s["tid"].to(torch.int32), stable=True)
+    perm = perm.to(torch.int32)
+    runs = []
+    for _ in range(2):
+        o = embed_bwd_operands(e, s, d, two=True, dpos=True, dword_fill=fill)
+        scratch = out_slab((T, d), F32, "dz_scratch")
+        _C.check(L().cx_embed_ln_bwd_sorted(*o["args"], V, sids.data_ptr(), perm.data_ptr(), scratch.ptr, S()), "embed_ln_bwd_sorted")
+        runs.append((o, scratch))
+    o, scratch = runs[0]
+    assert torch.equal(R.bits(o["dword"].t), R.bits(runs[1][0]["dword"].t)), "the sorted reduction is bit-reproducible"
+    assert torch.equal(R.bits(scratch.t), R.bits(runs[1][1].t))
+    r = check_embed_bwd(e, s, o, "embed_sorted", dword_fill=fill)
+    r["dz"] = R.check_result("embed_sorted.dz_scratch", scratch.t, o["ref"].dz, o["ref"].scale, C("embed_bwd", "dz"))
+    want, counts = sorted_scatter_of(scratch.t, s["tid"], fill, V)
+    assert counts[5] >= 40 and counts[8195] >= 9 and 2 <= counts[7] <= 4 and 0 in counts and 1 in counts
+    assert all(counts[v] > 0 for v in (0, 1, 2, 4, 5, 6, 7)) and all(c > 0 for c in counts[8192:]), "both rows of a two-row block"
+    assert torch.equal(R.bits(o["dword"].t.cpu()), R.bits(want)), "dword += the rows in the kernel's order, one add per row"
+    report("ln_edges.cx_embed_ln_bwd_sorted", d=d, T=T, vocab=V, **r)
 
 
 # -------------------------------------------------------------------------------------------------- unsupported width

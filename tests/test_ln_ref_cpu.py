@@ -165,7 +165,8 @@ def ratio_cols(got32, ref, abs_sum):
 
 
 def measure():
-    """C_meas of every family over MEASURE_ROWS x WIDTHS (and POOL_LENS), on the inputs of the GPU tests."""
+    """C_meas of every family over MEASURE_ROWS x WIDTHS (and POOL_LENS; the embedding families: the shapes of their GPU
+    tests), on the inputs of the GPU tests."""
     m = {k: dict.fromkeys(v, 0.0) for k, v in R.C_MEAS.items()}
 
     def up(fam, **kw):
@@ -231,6 +232,31 @@ def measure():
                     up("pooled", dz=ratio_result(o, ref.dz, ref.scale), dgamma=ratio_cols(dg, ref.dgamma, ref.dgamma_abs),
                        dbeta=ratio_cols(dbt, ref.dbeta, ref.dbeta_abs),
                        colsum=ratio_cols(st.float().sum(0), st.double().sum(0), st.double().abs().sum(0)))
+    for T, d in R.EMBED_FWD_SHAPES:
+        e = R.embed_fwd_inputs(T, d)
+        for pos in (e["pos"], None):
+            z, _, _ = R.embed_z(e["word"], e["type"], pos, e["ids"], e["indices"], e["seq"])
+            f = R.ln_fwd_ref(z, None, e["gamma"], e["beta"], 1e-12)
+            _, mean, rstd, out = emu_fwd(z, None, e["gamma"], e["beta"], 1e-12)
+            cm, cr = ratio_stats(mean, rstd, f)
+            up("embed_fwd", out=ratio_result(out, f.out, f.scale), out_tight=ratio_result(out, f.out, f.scale_tight), mean=cm, rstd=cr)
+    for e in [R.embed_bwd_inputs(d) for d in WIDTHS] + [R.embed_sorted_inputs(768)]:
+        for pos in (e["pos"], None):
+            z, tid, p = R.embed_z(e["word"], e["type"], pos, e["ids"], e["indices"], e["seq"])
+            st = R.ln_fwd_ref(z, None, e["gamma"], None, 1e-12)
+            mean, rstd = st.mean.float(), st.rstd.float()
+            for two in (True, False):
+                ref = R.ln_bwd_ref(e["da"], e["db"] if two else None, z, e["gamma"], mean, rstd, None)
+                dy = e["da"].float() + e["db"].float() if two else e["da"].float()
+                o, dg, dbt = emu_bwd(dy, z, e["gamma"], mean, rstd, None)
+                real = tid != R.EMBED_PAD
+                sc = max(ratio_cols(o.sum(0), ref.dz.sum(0), ref.scale.sum(0)),
+                         _ratio((R.scatter_rows(o, p, e["seq"]).double() - R.scatter_rows(ref.dz, p, e["seq"])).abs(),
+                                R.scatter_rows(ref.scale, p, e["seq"])).max(),
+                         _ratio((R.scatter_rows(o[real], tid[real], e["vocab"]).double() - R.scatter_rows(ref.dz[real], tid[real], e["vocab"])).abs(),
+                                R.scatter_rows(ref.scale[real], tid[real], e["vocab"])).max())
+                up("embed_bwd", dz=ratio_result(o, ref.dz, ref.scale, torch.float32), dgamma=ratio_cols(dg, ref.dgamma, ref.dgamma_abs),
+                   dbeta=ratio_cols(dbt, ref.dbeta, ref.dbeta_abs), scatter=float(sc))
     return m
 
 
