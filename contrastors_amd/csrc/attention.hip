@@ -24,18 +24,6 @@ constexpr float LN2 = 0.6931471805599453f;
 // probability (<= 1, flushed to 0 below 2^-126 either way once rounded to bf16) does not need.
 CX_DEVICE float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-CX_DEVICE void unpack8(const uint4& v, float (&f)[8]) {
-    f[0] = bf16lo_to_f32(v.x); f[1] = bf16hi_to_f32(v.x);
-    f[2] = bf16lo_to_f32(v.y); f[3] = bf16hi_to_f32(v.y);
-    f[4] = bf16lo_to_f32(v.z); f[5] = bf16hi_to_f32(v.z);
-    f[6] = bf16lo_to_f32(v.w); f[7] = bf16hi_to_f32(v.w);
-}
-CX_DEVICE uint4 pack8(const float (&f)[8]) {
-    uint4 v;
-    v.x = pack_bf16x2(f[0], f[1]); v.y = pack_bf16x2(f[2], f[3]);
-    v.z = pack_bf16x2(f[4], f[5]); v.w = pack_bf16x2(f[6], f[7]);
-    return v;
-}
 CX_DEVICE uint16_t elem16(const uint4& v, int e) {
     const uint32_t w = (e < 2) ? v.x : (e < 4) ? v.y : (e < 6) ? v.z : v.w;
     return (uint16_t)((e & 1) ? (w >> 16) : (w & 0xffffu));
@@ -1246,7 +1234,6 @@ __global__ void attn_keep_mask_kernel(AttnParams p, unsigned char* keep, int B, 
 }
 #endif
 
-inline int done() { return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
 
 // ------------------------------------------------------------------------ forward, sequences <= 128, lean-VALU form
 // attn_fwd_s128_kernel issues ~950 VALU instructions per problem and wave against 32 MFMAs and stores its output as

@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/contrastors_hip.h"
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits; all bf16 tensors cross the C-ABI as uint16_t*
 
@@ -35,6 +36,35 @@ CX_DEVICE uint32_t pack_bf16x2(float lo, float hi) {
 }
 CX_DEVICE bf16_t f32_to_bf16(float f) { return (bf16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }
 
+// One lane's 16 B of the HBM-bound kernels: 8 bf16 of a uint4 as 8 floats and back (one rounding per value), and 8
+// consecutive fp32 of a bias / gamma / beta vector as two 16-B loads, not eight scalar ones (bias_gelu_fwd was
+// VMEM-issue-bound on them).
+CX_DEVICE void unpack8(const uint4& v, float (&f)[8]) {
+    f[0] = bf16lo_to_f32(v.x); f[1] = bf16hi_to_f32(v.x);
+    f[2] = bf16lo_to_f32(v.y); f[3] = bf16hi_to_f32(v.y);
+    f[4] = bf16lo_to_f32(v.z); f[5] = bf16hi_to_f32(v.z);
+    f[6] = bf16lo_to_f32(v.w); f[7] = bf16hi_to_f32(v.w);
+}
+CX_DEVICE uint4 pack8(const float (&f)[8]) {
+    uint4 v;
+    v.x = pack_bf16x2(f[0], f[1]); v.y = pack_bf16x2(f[2], f[3]);
+    v.z = pack_bf16x2(f[4], f[5]); v.w = pack_bf16x2(f[6], f[7]);
+    return v;
+}
+CX_DEVICE void load8_f32(const float* p, float (&f)[8]) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+}
+
+// column of y / gate for activation column c of a (T, 2I) fc1 output: concatenated [y | gate] (layout 0) or interleaved in
+// groups of 32 ([y 0..31 | gate 0..31 | y 32..63 | ...], layout 1 = what the fused GEMM epilogue and its weight use)
+CX_DEVICE int ycol(int c, int I, int layout) { return layout ? ((c >> 5) << 6) + (c & 31) : c; }
+CX_DEVICE int gcol(int c, int I, int layout) { return layout ? ((c >> 5) << 6) + 32 + (c & 31) : I + c; }
+
+// sigmoid on v_exp_f32 + v_rcp_f32 (1 ulp each): an IEEE division costs ~10 VALU ops per element, which made the SwiGLU
+// backward kernel VALU-bound before it was HBM-bound
+CX_DEVICE float sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
+
 // The rotary rotation of one (x1, x2) pair in ONE fixed fp32 operation order: the second product is rounded by itself, the
 // first is fused into the sum (a v_mul_f32 and a v_fma_f32 per result: the instruction count of the contracted form, no time
 // lost in scripts/attn_microbench.py).  Every kernel that rotates q / k goes through here, because the result is rounded to bf16 next and a value
@@ -63,13 +93,14 @@ CX_DEVICE void rotary_pair(float x1, float x2, float c, float s, float& o1, floa
 // (tests/test_elementwise_edges_gpu.py, the saturation family).  Only the inf of a zero or denormal gate is clamped.
 CX_DEVICE float rcp_clamped(float g) { return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(g), -3.4028235e38f, 3.4028235e38f); }
 CX_DEVICE void swiglu_bwd_from_act(float d, float act, float g, float& dy, float& dg) {
-    const float s = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g));
+    const float s = sigmoid_fast(g);
     dy = g * s * d;
     dg = (d * act) * (rcp_clamped(g) + 1.f - s);
 }
 // The same on element PAIRS (v_pk_mul_f32 / v_pk_add_f32: two lanes' worth of fp32 per instruction; the transcendental and
 // median instructions have no packed form).  Same operations in the same order per element: bit-identical to the
-// scalar form.
+// scalar form.  sigmoid_fast is spelled out on the pair here: through the scalar helper the GEMM epilogues compile to scalar
+// v_mul_f32 / v_add_f32 (a fifth of their packed multiplies and a third of their packed adds gone).
 typedef float cx_f2 __attribute__((ext_vector_type(2)));
 CX_DEVICE void swiglu_bwd_from_act2(cx_f2 d, cx_f2 act, cx_f2 g, cx_f2& dy, cx_f2& dg) {
     const cx_f2 m = g * -1.4426950408889634f;
@@ -199,9 +230,12 @@ CX_DEVICE void dropout_keep4(const CxDropout& d, uint32_t site, unsigned long lo
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side: opt a kernel into > 64 KiB of dynamic LDS.  The attribute is per device, so it is remembered per device
-// index (the deployment is one process per GPU, but nothing in the library may silently depend on that).
+// host side: the C-ABI status of the launch just made, and the opt-in of a kernel into > 64 KiB of dynamic LDS.  The
+// attribute is per device, so it is remembered per device index (the deployment is one process per GPU, but nothing in
+// the library may silently depend on that).
 // ---------------------------------------------------------------------------------------------
+inline int done(hipError_t e = hipGetLastError()) { return e == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
+
 struct CxLdsOptIn {
     bool done[32] = {};
     bool ensure(const void* fn, int bytes) {

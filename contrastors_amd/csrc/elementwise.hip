@@ -8,19 +8,6 @@ namespace {
 
 constexpr int EW_BLOCK = 256;
 
-CX_DEVICE void unpack8(const uint4& v, float (&f)[8]) {
-    f[0] = bf16lo_to_f32(v.x); f[1] = bf16hi_to_f32(v.x);
-    f[2] = bf16lo_to_f32(v.y); f[3] = bf16hi_to_f32(v.y);
-    f[4] = bf16lo_to_f32(v.z); f[5] = bf16hi_to_f32(v.z);
-    f[6] = bf16lo_to_f32(v.w); f[7] = bf16hi_to_f32(v.w);
-}
-CX_DEVICE uint4 pack8(const float (&f)[8]) {
-    uint4 v;
-    v.x = pack_bf16x2(f[0], f[1]); v.y = pack_bf16x2(f[2], f[3]);
-    v.z = pack_bf16x2(f[4], f[5]); v.w = pack_bf16x2(f[6], f[7]);
-    return v;
-}
-
 // ------------------------------------------------------------------------------------------ transposes
 __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __restrict__ in, bf16_t* __restrict__ out,
                                                              int rows, int cols, int ld_in, int ld_out,
@@ -52,22 +39,30 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __res
     }
 }
 
-__global__ __launch_bounds__(256) void cast_transpose_f32_bf16_kernel(const float* __restrict__ in,
-                                                                      bf16_t* __restrict__ out, int rows, int cols) {
-    __shared__ float tile[64][65];
+// The 64 x 64 fp32 tile at (r0, c0) of a rows x cols matrix through LDS: element (gr, gc) is read as ld(gr, gc) and leaves
+// as st(gc, gr, value), both sides in runs of 64 consecutive lanes.
+template <typename Ld, typename St>
+CX_DEVICE void transpose_tile_f32(float (&tile)[64][65], int r0, int c0, int rows, int cols, Ld ld, St st) {
     const int tid = threadIdx.x;
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     for (int i = tid; i < 64 * 64; i += 256) {
         const int r = i >> 6, c = i & 63;
         const int gr = r0 + r, gc = c0 + c;
-        tile[r][c] = (gr < rows && gc < cols) ? in[(size_t)gr * cols + gc] : 0.f;
+        tile[r][c] = (gr < rows && gc < cols) ? ld(gr, gc) : 0.f;
     }
     __syncthreads();
     for (int i = tid; i < 64 * 64; i += 256) {
         const int c = i >> 6, r = i & 63;
         const int gr = r0 + r, gc = c0 + c;
-        if (gr < rows && gc < cols) out[(size_t)gc * rows + gr] = f32_to_bf16(tile[r][c]);
+        if (gr < rows && gc < cols) st(gc, gr, tile[r][c]);
     }
+}
+
+__global__ __launch_bounds__(256) void cast_transpose_f32_bf16_kernel(const float* __restrict__ in,
+                                                                      bf16_t* __restrict__ out, int rows, int cols) {
+    __shared__ float tile[64][65];
+    transpose_tile_f32(tile, blockIdx.y * 64, blockIdx.x * 64, rows, cols,
+                       [=](int gr, int gc) __attribute__((always_inline)) { return in[(size_t)gr * cols + gc]; },
+                       [=](int gc, int gr, float v) __attribute__((always_inline)) { out[(size_t)gc * rows + gr] = f32_to_bf16(v); });
 }
 
 // blockIdx.y = matrix, blockIdx.x = 64 x 64 tile of it (blocks past a matrix's tile count leave at once)
@@ -76,37 +71,17 @@ __global__ __launch_bounds__(256) void cast_transpose_batched_kernel(const CxCas
     const CxCastJob j = jobs[blockIdx.y];
     const int tiles_c = (j.cols + 63) / 64, tiles_r = (j.rows + 63) / 64;
     if ((int)blockIdx.x >= tiles_c * tiles_r) return;
-    const int tid = threadIdx.x;
-    const int r0 = (blockIdx.x / tiles_c) * 64, c0 = (blockIdx.x % tiles_c) * 64;
-    for (int i = tid; i < 64 * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        const int gr = r0 + r, gc = c0 + c;
-        tile[r][c] = (gr < j.rows && gc < j.cols) ? j.in[(size_t)gr * j.cols + gc] : 0.f;
-    }
-    __syncthreads();
-    for (int i = tid; i < 64 * 64; i += 256) {
-        const int c = i >> 6, r = i & 63;
-        const int gr = r0 + r, gc = c0 + c;
-        if (gr < j.rows && gc < j.cols) j.out_t[(size_t)gc * j.rows + gr] = f32_to_bf16(tile[r][c]);
-    }
+    transpose_tile_f32(tile, (blockIdx.x / tiles_c) * 64, (blockIdx.x % tiles_c) * 64, j.rows, j.cols,
+                       [=](int gr, int gc) __attribute__((always_inline)) { return j.in[(size_t)gr * j.cols + gc]; },
+                       [=](int gc, int gr, float v) __attribute__((always_inline)) { j.out_t[(size_t)gc * j.rows + gr] = f32_to_bf16(v); });
 }
 
 __global__ __launch_bounds__(256) void transpose_f32_kernel(const float* __restrict__ in, float* __restrict__ out,
                                                             int rows, int cols, int ld_in, int ld_out) {
     __shared__ float tile[64][65];
-    const int tid = threadIdx.x;
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    for (int i = tid; i < 64 * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        const int gr = r0 + r, gc = c0 + c;
-        tile[r][c] = (gr < rows && gc < cols) ? in[(size_t)gr * ld_in + gc] : 0.f;
-    }
-    __syncthreads();
-    for (int i = tid; i < 64 * 64; i += 256) {
-        const int c = i >> 6, r = i & 63;
-        const int gr = r0 + r, gc = c0 + c;
-        if (gr < rows && gc < cols) out[(size_t)gc * ld_out + gr] = tile[r][c];
-    }
+    transpose_tile_f32(tile, blockIdx.y * 64, blockIdx.x * 64, rows, cols,
+                       [=](int gr, int gc) __attribute__((always_inline)) { return in[(size_t)gr * ld_in + gc]; },
+                       [=](int gc, int gr, float v) __attribute__((always_inline)) { out[(size_t)gc * ld_out + gr] = v; });
 }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out,
@@ -132,44 +107,40 @@ __global__ __launch_bounds__(256) void cast_bf16_f32_kernel(const bf16_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------ activations
-// v_exp_f32 + v_rcp_f32 (1 ulp each): an IEEE division costs ~10 VALU ops per element, which made the SwiGLU backward
-// kernel VALU-bound before it was HBM-bound
-CX_DEVICE float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-
-// column of y / gate for activation column c: concatenated [y | gate] (layout 0) or interleaved in groups of 32
-// ([y 0..31 | gate 0..31 | y 32..63 | ...], layout 1 = what the fused GEMM epilogue and its weight use)
-CX_DEVICE int ycol(int c, int I, int layout) { return layout ? ((c >> 5) << 6) + (c & 31) : c; }
-CX_DEVICE int gcol(int c, int I, int layout) { return layout ? ((c >> 5) << 6) + 32 + (c & 31) : I + c; }
+// f(t, c) for every (row t, 8-column chunk at column c) of a (T, I) activation.  Flat grid-stride: consecutive lanes stream
+// consecutive 16-B chunks (a 2-D row-strided mapping measured 8-14 % slower at the same byte count).
+// The block size is read through the builtin: `blockDim.x` outside a kernel's own body compiled to the non-uniform-grid
+// form (a compare and a select on the block index, a 16-bit vector load and two VGPRs more in every caller).  The bodies are
+// [=] lambdas marked always_inline: in that form four kernels compile to the instructions of their written-out loops
+// (bias_gelu_bwd_kernel in another order); inlined later, or capturing by reference, they did not.
+template <typename F>
+CX_DEVICE void for_each_chunk(long T, int I, F f) {
+    const int chunks = I >> 3;
+    const long total = T * chunks;
+    const long stride = (long)gridDim.x * __builtin_amdgcn_workgroup_size_x();
+    for (long i = (long)blockIdx.x * __builtin_amdgcn_workgroup_size_x() + threadIdx.x; i < total; i += stride) {
+        const long t = i / chunks;
+        f(t, (int)(i - t * chunks) * 8);
+    }
+}
 
 __global__ __launch_bounds__(256) void swiglu_fwd_kernel(const bf16_t* __restrict__ yg, bf16_t* __restrict__ act,
                                                          long T, int I, int layout) {
-    const int chunks = I >> 3;
-    const long total = T * chunks;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long t = i / chunks;
-        const int c = (int)(i - t * chunks) * 8;
+    for_each_chunk(T, I, [=](long t, int c) __attribute__((always_inline)) {
         const bf16_t* row = yg + t * (2L * I);
         float y[8], g[8], o[8];
         unpack8(*reinterpret_cast<const uint4*>(row + ycol(c, I, layout)), y);
         unpack8(*reinterpret_cast<const uint4*>(row + gcol(c, I, layout)), g);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = g[e] * sigmoidf_(g[e]) * y[e];
+        for (int e = 0; e < 8; ++e) o[e] = g[e] * sigmoid_fast(g[e]) * y[e];
         *reinterpret_cast<uint4*>(act + t * (long)I + c) = pack8(o);
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restrict__ dact,
                                                          const bf16_t* __restrict__ yg, bf16_t* __restrict__ dyg,
                                                          long T, int I, int layout) {
-    // flat grid-stride over (row, 8-column chunk): consecutive lanes stream consecutive 16-B chunks (a 2-D row-strided
-    // mapping measured 8-14 % slower at the same byte count)
-    const int chunks = I >> 3;
-    const long total = T * chunks;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long t = i / chunks;
-        const int c = (int)(i - t * chunks) * 8;
+    for_each_chunk(T, I, [=](long t, int c) __attribute__((always_inline)) {
         const bf16_t* row = yg + t * (2L * I);
         float y[8], g[8], d[8], dy[8], dg[8];
         unpack8(*reinterpret_cast<const uint4*>(row + ycol(c, I, layout)), y);
@@ -177,7 +148,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restric
         unpack8(*reinterpret_cast<const uint4*>(dact + t * (long)I + c), d);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            const float s = sigmoidf_(g[e]);
+            const float s = sigmoid_fast(g[e]);
             const float gs = g[e] * s;
             dy[e] = gs * d[e];
             dg[e] = (s + gs * (1.f - s)) * d[e] * y[e];
@@ -185,7 +156,7 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restric
         bf16_t* orow = dyg + t * (2L * I);
         *reinterpret_cast<uint4*>(orow + ycol(c, I, layout)) = pack8(dy);
         *reinterpret_cast<uint4*>(orow + gcol(c, I, layout)) = pack8(dg);
-    }
+    });
 }
 
 // SwiGLU backward from (act, gate): the forward saved the gate alone next to the activation (cx_gemm_bf16_swiglu_gate);
@@ -194,6 +165,8 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const bf16_t* __restric
 __global__ __launch_bounds__(256) void swiglu_bwd_gate_kernel(const bf16_t* __restrict__ dact, const bf16_t* __restrict__ act,
                                                               const bf16_t* __restrict__ gate, bf16_t* __restrict__ dyg,
                                                               long T, int I) {
+    // (the walk of for_each_chunk written out: through the helper the compiler packs this body's fp32 pairs differently --
+    // another instruction mix, one more VGPR)
     const int chunks = I >> 3;
     const long total = T * chunks;
     const long stride = (long)gridDim.x * blockDim.x;
@@ -216,54 +189,31 @@ template <int kind>
 __global__ __launch_bounds__(256) void bias_gelu_fwd_kernel(const bf16_t* __restrict__ pre,
                                                             const float* __restrict__ bias,
                                                             bf16_t* __restrict__ act, long T, int I) {
-    const int chunks = I >> 3;
-    const long total = T * chunks;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long t = i / chunks;
-        const int c = (int)(i - t * chunks) * 8;
+    for_each_chunk(T, I, [=](long t, int c) __attribute__((always_inline)) {
         float x[8], o[8];
         unpack8(*reinterpret_cast<const uint4*>(pre + t * (long)I + c), x);
         float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (bias) {  // two 16-B loads, not eight scalar ones (the kernel was VMEM-issue-bound on them)
-            const float4 b0 = *reinterpret_cast<const float4*>(bias + c), b1 = *reinterpret_cast<const float4*>(bias + c + 4);
-            bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
-        }
+        if (bias) load8_f32(bias + c, bb);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            o[e] = act_val(x[e] + bb[e], kind);
-        }
+        for (int e = 0; e < 8; ++e) o[e] = act_val(x[e] + bb[e], kind);
         *reinterpret_cast<uint4*>(act + t * (long)I + c) = pack8(o);
-    }
+    });
 }
 
 __global__ __launch_bounds__(256) void bias_gelu_bwd_kernel(const bf16_t* __restrict__ dact,
                                                             const bf16_t* __restrict__ pre,
                                                             const float* __restrict__ bias,
                                                             bf16_t* __restrict__ dpre, long T, int I) {
-    const int chunks = I >> 3;
-    const long total = T * chunks;
-    const long stride = (long)gridDim.x * blockDim.x;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const long t = i / chunks;
-        const int c = (int)(i - t * chunks) * 8;
+    for_each_chunk(T, I, [=](long t, int c) __attribute__((always_inline)) {
         float x[8], d[8], o[8];
         unpack8(*reinterpret_cast<const uint4*>(pre + t * (long)I + c), x);
         unpack8(*reinterpret_cast<const uint4*>(dact + t * (long)I + c), d);
         float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (bias) {
-            const float4 b0 = *reinterpret_cast<const float4*>(bias + c), b1 = *reinterpret_cast<const float4*>(bias + c + 4);
-            bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
-        }
+        if (bias) load8_f32(bias + c, bb);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float v = x[e] + bb[e];
-            float gauss;
-            const float cdf = gelu_cdf(v, gauss);
-            o[e] = d[e] * (cdf + v * 0.3989422804014327f * gauss);
-        }
+        for (int e = 0; e < 8; ++e) o[e] = d[e] * act_grad(x[e] + bb[e], CX_ACT_GELU);
         *reinterpret_cast<uint4*>(dpre + t * (long)I + c) = pack8(o);
-    }
+    });
 }
 
 // dbias[n] += sum_t dY[t][n].  Block = 32 column-chunks (256 columns) x 8 row lanes; every thread keeps four 16-byte loads
@@ -282,10 +232,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ 
     float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (col < N) {
         float bb[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (GELU && bias) {
-            const float4 b0 = *reinterpret_cast<const float4*>(bias + col), b1 = *reinterpret_cast<const float4*>(bias + col + 4);
-            bb[0] = b0.x; bb[1] = b0.y; bb[2] = b0.z; bb[3] = b0.w; bb[4] = b1.x; bb[5] = b1.y; bb[6] = b1.z; bb[7] = b1.w;
-        }
+        if (GELU && bias) load8_f32(bias + col, bb);
         const int step = gridDim.y * 8;
         constexpr int U = GELU ? 2 : 4;
         for (int t0 = blockIdx.y * 8 + rl; t0 < T; t0 += U * step) {
@@ -451,7 +398,12 @@ inline int grid_for(long total_threads) {
     if (g < 1) g = 1;
     return (int)g;
 }
-inline int done(hipError_t e = hipGetLastError()) { return e == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
+// the CX_ACT_QUICK_GELU or the CX_ACT_GELU instantiation of an activation-templated kernel, by the run-time `act`
+template <typename K, typename... A>
+int launch_act(int act, K quick_gelu, K gelu, dim3 grid, void* stream, A... args) {
+    hipLaunchKernelGGL(act == CX_ACT_QUICK_GELU ? quick_gelu : gelu, grid, dim3(256), 0, (hipStream_t)stream, args...);
+    return done();
+}
 
 }  // namespace
 
@@ -537,13 +489,8 @@ int cx_bias_act_fwd(const uint16_t* pre, const float* bias, uint16_t* act_out, i
     if (T <= 0) return CX_OK;
     if (I % 8) return CX_ERR_SHAPE;
     if (act != CX_ACT_GELU && act != CX_ACT_QUICK_GELU) return CX_ERR_ARG;
-    if (act == CX_ACT_QUICK_GELU)
-        hipLaunchKernelGGL(bias_gelu_fwd_kernel<CX_ACT_QUICK_GELU>, dim3(grid_for((long)T * (I / 8))), dim3(EW_BLOCK), 0,
-                           (hipStream_t)stream, pre, bias, act_out, (long)T, I);
-    else
-        hipLaunchKernelGGL(bias_gelu_fwd_kernel<CX_ACT_GELU>, dim3(grid_for((long)T * (I / 8))), dim3(EW_BLOCK), 0,
-                           (hipStream_t)stream, pre, bias, act_out, (long)T, I);
-    return done();
+    return launch_act(act, bias_gelu_fwd_kernel<CX_ACT_QUICK_GELU>, bias_gelu_fwd_kernel<CX_ACT_GELU>,
+                      dim3(grid_for((long)T * (I / 8))), stream, pre, bias, act_out, (long)T, I);
 }
 
 int cx_bias_gelu_bwd(const uint16_t* dact, const uint16_t* pre, const float* bias, uint16_t* dpre, int T, int I,
@@ -586,13 +533,8 @@ int cx_bias_act_bwd_colsum(const uint16_t* dact, const uint16_t* pre, const floa
     if (I % 8) return CX_ERR_SHAPE;
     if (!dact || !pre || !dpre || (act != CX_ACT_GELU && act != CX_ACT_QUICK_GELU)) return CX_ERR_ARG;
     dim3 grid((I + 255) / 256, colsum_rows_grid(T, I));
-    if (act == CX_ACT_QUICK_GELU)
-        hipLaunchKernelGGL((colsum_kernel<true, CX_ACT_QUICK_GELU>), grid, dim3(256), 0, (hipStream_t)stream, dact, pre, bias, dpre,
-                           dbias, T, I, I);
-    else
-        hipLaunchKernelGGL((colsum_kernel<true, CX_ACT_GELU>), grid, dim3(256), 0, (hipStream_t)stream, dact, pre, bias, dpre, dbias,
-                           T, I, I);
-    return done();
+    return launch_act(act, colsum_kernel<true, CX_ACT_QUICK_GELU>, colsum_kernel<true, CX_ACT_GELU>, grid, stream, dact, pre, bias,
+                      dpre, dbias, T, I, I);
 }
 
 int cx_pool_normalize_fwd(const uint16_t* h, const int32_t* cu_seqlens, float* emb, float* norm, int B, int d,

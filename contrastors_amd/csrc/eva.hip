@@ -11,22 +11,6 @@
 
 namespace {
 
-CX_DEVICE void unpack8e(const uint4& v, float (&f)[8]) {
-    f[0] = bf16lo_to_f32(v.x); f[1] = bf16hi_to_f32(v.x);
-    f[2] = bf16lo_to_f32(v.y); f[3] = bf16hi_to_f32(v.y);
-    f[4] = bf16lo_to_f32(v.z); f[5] = bf16hi_to_f32(v.z);
-    f[6] = bf16lo_to_f32(v.w); f[7] = bf16hi_to_f32(v.w);
-}
-CX_DEVICE uint4 pack8e(const float (&f)[8]) {
-    uint4 v;
-    v.x = pack_bf16x2(f[0], f[1]); v.y = pack_bf16x2(f[2], f[3]);
-    v.z = pack_bf16x2(f[4], f[5]); v.w = pack_bf16x2(f[6], f[7]);
-    return v;
-}
-// column of y / gate element c of an (T, 2I) fc1 output in the interleaved-by-32 layout of the fused fc1 weight
-CX_DEVICE int ycol_i(int c) { return ((c >> 5) << 6) + (c & 31); }
-CX_DEVICE int gcol_i(int c) { return ((c >> 5) << 6) + 32 + (c & 31); }
-
 // ---- 2-D RoPE ------------------------------------------------------------------------------------------------------
 // Block (bx, by): row y of the block owns token t = blockIdx.x * by + y, its bx threads walk the 8-column groups of [q | k]
 // (4 rotation pairs of one head each).  Token t belongs to the sequence b with cu[b] <= t < cu[b + 1]; the search over
@@ -68,14 +52,14 @@ __global__ __launch_bounds__(1024) void rope2d_kernel(bf16_t* __restrict__ qkv, 
         const float si[4] = {sgn * s4.x, sgn * s4.y, sgn * s4.z, sgn * s4.w};
         bf16_t* ptr = qkv + (size_t)t * 3 * d + c;
         float x[8], o[8];
-        unpack8e(*reinterpret_cast<const uint4*>(ptr), x);
+        unpack8(*reinterpret_cast<const uint4*>(ptr), x);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float x0 = x[2 * j], x1 = x[2 * j + 1];
             o[2 * j] = x0 * co[j] + (-x1) * si[j];   // (fp contract off: two roundings of the products, one of the sum)
             o[2 * j + 1] = x1 * co[j] + x0 * si[j];
         }
-        *reinterpret_cast<uint4*>(ptr) = pack8e(o);
+        *reinterpret_cast<uint4*>(ptr) = pack8(o);
     }
 }
 
@@ -97,8 +81,6 @@ CX_DEVICE float2 block_sum2(float a, float b, float2* red) {
     return s;
 }
 
-CX_DEVICE float silu_sig(float g) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g)); }
-
 // a = bf16(silu(gate) * y), z = LN_I(a) * gamma + beta.  The statistics are taken over the ROUNDED a (what the next op of the
 // reference reads), two passes in registers.
 __global__ __launch_bounds__(512) void swiglu_subln_fwd_kernel(const bf16_t* __restrict__ yg, const float* __restrict__ gamma,
@@ -113,16 +95,16 @@ __global__ __launch_bounds__(512) void swiglu_subln_fwd_kernel(const bf16_t* __r
     float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (has) {
         const bf16_t* row = yg + t * (2L * I);
-        const uint4 gu = *reinterpret_cast<const uint4*>(row + gcol_i(c));
+        const uint4 gu = *reinterpret_cast<const uint4*>(row + gcol(c, I, 1));
         float y[8], g[8], o[8];
-        unpack8e(*reinterpret_cast<const uint4*>(row + ycol_i(c)), y);
-        unpack8e(gu, g);
+        unpack8(*reinterpret_cast<const uint4*>(row + ycol(c, I, 1)), y);
+        unpack8(gu, g);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = g[e] * silu_sig(g[e]) * y[e];
-        const uint4 au = pack8e(o);
+        for (int e = 0; e < 8; ++e) o[e] = g[e] * sigmoid_fast(g[e]) * y[e];
+        const uint4 au = pack8(o);
         *reinterpret_cast<uint4*>(act_out + t * (long)I + c) = au;
         if (gate_out) *reinterpret_cast<uint4*>(gate_out + t * (long)I + c) = gu;
-        unpack8e(au, a);
+        unpack8(au, a);
     }
     float s = 0.f;
 #pragma unroll
@@ -135,14 +117,12 @@ __global__ __launch_bounds__(512) void swiglu_subln_fwd_kernel(const bf16_t* __r
     }
     const float rstd = rsqrtf(block_sum2(v, 0.f, red).x / (float)I + eps);
     if (has) {
-        const float4 g0 = *reinterpret_cast<const float4*>(gamma + c), g1 = *reinterpret_cast<const float4*>(gamma + c + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(beta + c), b1 = *reinterpret_cast<const float4*>(beta + c + 4);
-        const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
-        const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-        float z[8];
+        float gg[8], bb[8], z[8];
+        load8_f32(gamma + c, gg);
+        load8_f32(beta + c, bb);
 #pragma unroll
         for (int e = 0; e < 8; ++e) z[e] = (a[e] - mean) * rstd * gg[e] + bb[e];
-        *reinterpret_cast<uint4*>(z_out + t * (long)I + c) = pack8e(z);
+        *reinterpret_cast<uint4*>(z_out + t * (long)I + c) = pack8(z);
     }
     if (threadIdx.x == 0) {
         mean_o[t] = mean;
@@ -164,10 +144,7 @@ __global__ __launch_bounds__(512) void swiglu_subln_bwd_kernel(const bf16_t* __r
     const long r0 = (long)blockIdx.x * rows_per;
     const long r1 = r0 + rows_per < T ? r0 + rows_per : T;
     float gg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (has) {
-        const float4 g0 = *reinterpret_cast<const float4*>(gamma + c), g1 = *reinterpret_cast<const float4*>(gamma + c + 4);
-        gg[0] = g0.x; gg[1] = g0.y; gg[2] = g0.z; gg[3] = g0.w; gg[4] = g1.x; gg[5] = g1.y; gg[6] = g1.z; gg[7] = g1.w;
-    }
+    if (has) load8_f32(gamma + c, gg);
     float acc_g[8], acc_b[8], acc_y[8], acc_t[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc_g[e] = acc_b[e] = acc_y[e] = acc_t[e] = 0.f;
@@ -175,9 +152,9 @@ __global__ __launch_bounds__(512) void swiglu_subln_bwd_kernel(const bf16_t* __r
         float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f},
               g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (has) {
-            unpack8e(*reinterpret_cast<const uint4*>(dz + t * (long)I + c), d);
-            unpack8e(*reinterpret_cast<const uint4*>(act + t * (long)I + c), a);
-            unpack8e(*reinterpret_cast<const uint4*>(gate + t * (long)I + c), g);
+            unpack8(*reinterpret_cast<const uint4*>(dz + t * (long)I + c), d);
+            unpack8(*reinterpret_cast<const uint4*>(act + t * (long)I + c), a);
+            unpack8(*reinterpret_cast<const uint4*>(gate + t * (long)I + c), g);
         }
         const float mu = mean_i[t], rs = rstd_i[t];
         float xh[8], dxh[8], s1 = 0.f, s2 = 0.f;
@@ -199,12 +176,12 @@ __global__ __launch_bounds__(512) void swiglu_subln_bwd_kernel(const bf16_t* __r
             const float da = rs * (dxh[e] - m1 - xh[e] * m2);
             swiglu_bwd_from_act(da, a[e], g[e], dy[e], dg[e]);
         }
-        const uint4 yu = pack8e(dy), gu = pack8e(dg);
+        const uint4 yu = pack8(dy), gu = pack8(dg);
         bf16_t* orow = dyg + t * (2L * I);
-        *reinterpret_cast<uint4*>(orow + ycol_i(c)) = yu;
-        *reinterpret_cast<uint4*>(orow + gcol_i(c)) = gu;
-        unpack8e(yu, dy);
-        unpack8e(gu, dg);
+        *reinterpret_cast<uint4*>(orow + ycol(c, I, 1)) = yu;
+        *reinterpret_cast<uint4*>(orow + gcol(c, I, 1)) = gu;
+        unpack8(yu, dy);
+        unpack8(gu, dg);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             acc_y[e] += dy[e];
@@ -217,8 +194,8 @@ __global__ __launch_bounds__(512) void swiglu_subln_bwd_kernel(const bf16_t* __r
     for (int e = 0; e < 8; ++e) {
         w[c + e] = acc_g[e];
         w[I + c + e] = acc_b[e];
-        w[2 * I + ycol_i(c) + e] = acc_y[e];
-        w[2 * I + gcol_i(c) + e] = acc_t[e];
+        w[2 * I + ycol(c, I, 1) + e] = acc_y[e];
+        w[2 * I + gcol(c, I, 1) + e] = acc_t[e];
     }
 }
 
@@ -239,7 +216,6 @@ __global__ __launch_bounds__(256) void swiglu_subln_reduce_kernel(const float* _
     }
 }
 
-inline int done() { return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
 inline bool subln_width_ok(int I) { return I > 0 && I <= 4096 && (I % 256) == 0; }
 
 }  // namespace

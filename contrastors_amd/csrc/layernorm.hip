@@ -827,7 +827,6 @@ inline int ln_grid(int rows) {
     if (g < 1) g = 1;
     return g;
 }
-inline int done() { return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
 
 // (variadic: a hipLaunchKernelGGL passed through a second macro arrives expanded, its commas bare)
 #define CX_LN_DISPATCH(d, ...)                                     \

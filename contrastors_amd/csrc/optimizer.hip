@@ -110,7 +110,7 @@ int cx_grad_sq_norm(const float* grad, long n, double* sq_norm_accum, void* stre
     if (!grad || !sq_norm_accum) return CX_ERR_ARG;
     if (!aligned16(grad)) return CX_ERR_SHAPE;
     hipLaunchKernelGGL(grad_sq_norm_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, grad, n, sq_norm_accum);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    return done();
 }
 
 int cx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
@@ -126,7 +126,7 @@ int cx_adamw_clip_step(float* param, const float* grad, float* exp_avg, float* e
     a.max_norm = max_norm;
     hipLaunchKernelGGL(adamw_clip_step_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                        exp_avg_sq, n, a, sq_norm);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    return done();
 }
 
 int cx_ema_update(float* ema, const float* param, long n, float decay, void* stream) {
@@ -134,7 +134,7 @@ int cx_ema_update(float* ema, const float* param, long n, float decay, void* str
     if (!ema || !param || !(decay >= 0.f) || decay > 1.f) return CX_ERR_ARG;
     if (!aligned16(ema) || !aligned16(param)) return CX_ERR_SHAPE;
     hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, ema, param, n, decay);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    return done();
 }
 
 }  // extern "C"

@@ -67,18 +67,13 @@ __global__ void vit_assemble_fwd_kernel(const bf16_t* __restrict__ proj, const f
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = cls[c8 * 8 + e];
     } else {
-        const uint4 u = *reinterpret_cast<const uint4*>(proj + ((size_t)b * P + (s - 1)) * d + c8 * 8);
-        v[0] = bf16lo_to_f32(u.x); v[1] = bf16hi_to_f32(u.x); v[2] = bf16lo_to_f32(u.y); v[3] = bf16hi_to_f32(u.y);
-        v[4] = bf16lo_to_f32(u.z); v[5] = bf16hi_to_f32(u.z); v[6] = bf16lo_to_f32(u.w); v[7] = bf16hi_to_f32(u.w);
+        unpack8(*reinterpret_cast<const uint4*>(proj + ((size_t)b * P + (s - 1)) * d + c8 * 8), v);
     }
     const int ps = (s > 0 && keep) ? 1 + keep[(size_t)b * P + (s - 1)] : s;
     const float* pp = pos + (size_t)ps * d + c8 * 8;
-    uint4 o;
-    o.x = pack_bf16x2(v[0] + pp[0], v[1] + pp[1]);
-    o.y = pack_bf16x2(v[2] + pp[2], v[3] + pp[3]);
-    o.z = pack_bf16x2(v[4] + pp[4], v[5] + pp[5]);
-    o.w = pack_bf16x2(v[6] + pp[6], v[7] + pp[7]);
-    *reinterpret_cast<uint4*>(out + (size_t)row * d + c8 * 8) = o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += pp[e];
+    *reinterpret_cast<uint4*>(out + (size_t)row * d + c8 * 8) = pack8(v);
 }
 
 // Backward of the assembly.  Grid (d/8 column groups, P+1 sequence positions); each thread walks the batch:
@@ -103,8 +98,10 @@ __global__ void vit_assemble_bwd_kernel(const bf16_t* __restrict__ dz, bf16_t* _
         }
         const uint4 u = *reinterpret_cast<const uint4*>(dz + ((size_t)b * (P + 1) + sk) * d + c8 * 8);
         if (s > 0) *reinterpret_cast<uint4*>(dproj + ((size_t)b * P + (sk - 1)) * d + c8 * 8) = u;
-        acc[0] += bf16lo_to_f32(u.x); acc[1] += bf16hi_to_f32(u.x); acc[2] += bf16lo_to_f32(u.y); acc[3] += bf16hi_to_f32(u.y);
-        acc[4] += bf16lo_to_f32(u.z); acc[5] += bf16hi_to_f32(u.z); acc[6] += bf16lo_to_f32(u.w); acc[7] += bf16hi_to_f32(u.w);
+        float v[8];
+        unpack8(u, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += v[e];
     }
     if (gpos) {
 #pragma unroll
@@ -115,8 +112,6 @@ __global__ void vit_assemble_bwd_kernel(const bf16_t* __restrict__ dz, bf16_t* _
         for (int e = 0; e < 8; ++e) gcls[c8 * 8 + e] += acc[e];
     }
 }
-
-inline int done() { return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
 
 }  // namespace
 

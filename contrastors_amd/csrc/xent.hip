@@ -37,9 +37,7 @@ CX_DEVICE void ld_vec(const T* p, long i, float (&v)[VEC]) {
         const float4 u = *reinterpret_cast<const float4*>(p + i);
         v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
     } else {
-        const uint4 u = *reinterpret_cast<const uint4*>(p + i);
-        v[0] = bf16lo_to_f32(u.x); v[1] = bf16hi_to_f32(u.x); v[2] = bf16lo_to_f32(u.y); v[3] = bf16hi_to_f32(u.y);
-        v[4] = bf16lo_to_f32(u.z); v[5] = bf16hi_to_f32(u.z); v[6] = bf16lo_to_f32(u.w); v[7] = bf16hi_to_f32(u.w);
+        unpack8(*reinterpret_cast<const uint4*>(p + i), v);
     }
 }
 template <typename T, int VEC>
@@ -49,10 +47,7 @@ CX_DEVICE void st_vec(T* p, long i, const float (&v)[VEC]) {
     } else if constexpr (sizeof(T) == 4) {
         *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
     } else {
-        uint4 u;
-        u.x = pack_bf16x2(v[0], v[1]); u.y = pack_bf16x2(v[2], v[3]);
-        u.z = pack_bf16x2(v[4], v[5]); u.w = pack_bf16x2(v[6], v[7]);
-        *reinterpret_cast<uint4*>(p + i) = u;
+        *reinterpret_cast<uint4*>(p + i) = pack8(v);
     }
 }
 
@@ -130,7 +125,18 @@ __global__ __launch_bounds__(XB) void xent_bwd_kernel(const float* __restrict__ 
     }
 }
 
-inline int done() { return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH; }
+// launch(T{}, VEC) with the logit type and the vector width of one launch: 16-byte accesses when `vec16` (every base pointer
+// is 16-byte aligned), V and both row strides allow them (the forward has one stride and passes it twice), else scalar
+template <typename F>
+void pick_kernel(int logits_bf16, bool vec16, int V, long ld, long ld_d, F launch) {
+    if (logits_bf16) {
+        if (vec16 && (V % 8) == 0 && (ld % 8) == 0 && (ld_d % 8) == 0) launch(bf16_t{}, std::integral_constant<int, 8>{});
+        else launch(bf16_t{}, std::integral_constant<int, 1>{});
+    } else {
+        if (vec16 && (V % 4) == 0 && (ld % 4) == 0 && (ld_d % 4) == 0) launch(float{}, std::integral_constant<int, 4>{});
+        else launch(float{}, std::integral_constant<int, 1>{});
+    }
+}
 
 }  // namespace
 
@@ -142,21 +148,11 @@ int cx_xent_fwd(const void* logits, int logits_bf16, const int64_t* labels, floa
     if (!logits || !labels || !loss || !lse) return CX_ERR_ARG;
     if (V <= 0 || ld < V) return CX_ERR_SHAPE;
     const bool vec16 = ((uintptr_t)logits % 16) == 0;
-    if (logits_bf16) {
-        if (vec16 && (V % 8) == 0 && (ld % 8) == 0)
-            hipLaunchKernelGGL((xent_fwd_kernel<bf16_t, 8>), dim3(N), dim3(XB), 0, (hipStream_t)stream, (const bf16_t*)logits,
-                               labels, loss, lse, V, ld, logit_scale, ignore_index);
-        else
-            hipLaunchKernelGGL((xent_fwd_kernel<bf16_t, 1>), dim3(N), dim3(XB), 0, (hipStream_t)stream, (const bf16_t*)logits,
-                               labels, loss, lse, V, ld, logit_scale, ignore_index);
-    } else {
-        if (vec16 && (V % 4) == 0 && (ld % 4) == 0)
-            hipLaunchKernelGGL((xent_fwd_kernel<float, 4>), dim3(N), dim3(XB), 0, (hipStream_t)stream, (const float*)logits,
-                               labels, loss, lse, V, ld, logit_scale, ignore_index);
-        else
-            hipLaunchKernelGGL((xent_fwd_kernel<float, 1>), dim3(N), dim3(XB), 0, (hipStream_t)stream, (const float*)logits,
-                               labels, loss, lse, V, ld, logit_scale, ignore_index);
-    }
+    pick_kernel(logits_bf16, vec16, V, ld, ld, [&](auto t, auto vec) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((xent_fwd_kernel<T, vec()>), dim3(N), dim3(XB), 0, (hipStream_t)stream, (const T*)logits, labels, loss,
+                           lse, V, ld, logit_scale, ignore_index);
+    });
     return done();
 }
 
@@ -166,21 +162,11 @@ int cx_xent_bwd(const float* dloss, const void* logits, int logits_bf16, const f
     if (!dloss || !logits || !lse || !labels || !dlogits) return CX_ERR_ARG;
     if (V <= 0 || ld < V || ld_d < V) return CX_ERR_SHAPE;
     const bool vec16 = ((uintptr_t)logits % 16) == 0 && ((uintptr_t)dlogits % 16) == 0;
-    if (logits_bf16) {
-        if (vec16 && (V % 8) == 0 && (ld % 8) == 0 && (ld_d % 8) == 0)
-            hipLaunchKernelGGL((xent_bwd_kernel<bf16_t, 8>), dim3(N), dim3(XB), 0, (hipStream_t)stream, dloss,
-                               (const bf16_t*)logits, lse, labels, (bf16_t*)dlogits, V, ld, ld_d, logit_scale, ignore_index);
-        else
-            hipLaunchKernelGGL((xent_bwd_kernel<bf16_t, 1>), dim3(N), dim3(XB), 0, (hipStream_t)stream, dloss,
-                               (const bf16_t*)logits, lse, labels, (bf16_t*)dlogits, V, ld, ld_d, logit_scale, ignore_index);
-    } else {
-        if (vec16 && (V % 4) == 0 && (ld % 4) == 0 && (ld_d % 4) == 0)
-            hipLaunchKernelGGL((xent_bwd_kernel<float, 4>), dim3(N), dim3(XB), 0, (hipStream_t)stream, dloss,
-                               (const float*)logits, lse, labels, (float*)dlogits, V, ld, ld_d, logit_scale, ignore_index);
-        else
-            hipLaunchKernelGGL((xent_bwd_kernel<float, 1>), dim3(N), dim3(XB), 0, (hipStream_t)stream, dloss,
-                               (const float*)logits, lse, labels, (float*)dlogits, V, ld, ld_d, logit_scale, ignore_index);
-    }
+    pick_kernel(logits_bf16, vec16, V, ld, ld_d, [&](auto t, auto vec) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((xent_bwd_kernel<T, vec()>), dim3(N), dim3(XB), 0, (hipStream_t)stream, dloss, (const T*)logits, lse, labels,
+                           (T*)dlogits, V, ld, ld_d, logit_scale, ignore_index);
+    });
     return done();
 }
 

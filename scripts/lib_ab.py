@@ -7,10 +7,14 @@ output is compared with the first library's (bit-identical or the max relative d
 `base` = contrastors_amd/lib/libcontrastors_hip.so; a name with a `/` is the path of a .so; any other name N =
 contrastors_amd/lib/variants/libcontrastors_hip_N.so.  Two copies of one build among the libraries give the yardstick for the
 others: the ratio between them, and the `spread` column (max - min over the median of the first library's per-round times), are
-what the box cannot tell from no change.  Operands are allocated only for the groups of cases selected (GEMM, attention, LayerNorm).
+what the box cannot tell from no change.  Operands are allocated only for the groups of cases selected (GEMM, attention, LayerNorm,
+glue kernels).
 The LayerNorm cases run at T = chunk * 128 rows of --width columns (the metric's 262144 x 768 by default) and report the bytes they
 must move as TB/s; each lists only its deterministic outputs (the atomically accumulated vectors are held to bounds by
-tests/test_layernorm_edges_gpu.py)."""
+tests/test_layernorm_edges_gpu.py).  The glue cases (elementwise.hip, eva.hip, vit.hip, xent.hip, optimizer.hip) run at the step's
+sizes too (T rows of I = 3072 or d = 768; cross-entropy on T / 8 rows of the 30528-way MLM vocabulary; AdamW on the parameter count
+of nomic-bert-2048) and report TB/s; cx_bias_grad and cx_grad_sq_norm accumulate atomically and are timed only.
+    python scripts/lib_ab.py --libs /path/to/parent.so,/path/to/parent_copy.so,base --cases glue"""
 import argparse
 import ctypes as C
 import sys
@@ -162,11 +166,114 @@ def ln_cases():
     }
 
 
-GROUPS = {gemm_cases: ("swiglu_bwd", "swiglu_fwd_save", "swiglu_fwd", "qkv_fwd", "out_dgrad", "out_fwd_res", "fc2_fwd_res", "qkv_dgrad_res", "fc1_dgrad_res"),
+def glue_cases():
+    f32, i32 = torch.float32, torch.int32
+    L0 = libs[names[0]]
+    Bt, Bd = 2.0 * T * I, 2.0 * T * d                     # bytes of one bf16 (T, I) / (T, d) operand
+    yg, dact, pre, gate = rn(T, 2 * I), rn(T, I), rn(T, I), rn(T, I, std=2.0)
+    act, bias = E(T, I), rf(I, std=0.1)
+    assert L0.cx_swiglu_fwd(P(yg), P(act), T, I, 1, s) == 0   # the (act, gate) pair of the gate-saving backward
+    dyg, o_I = E(T, 2 * I), E(T, I)
+    # casts and transposes: the fc1 weight (2I, d) and its 12 layers in one batched launch; the bf16 transpose on (T, d)
+    w32, x = rf(2 * I, d, std=0.05), rn(T, d)
+    wbf, w_back, wt, wt32, xt = E(2 * I, d), E(2 * I, d, dt=f32), E(d, 2 * I), E(d, 2 * I, dt=f32), E(d, T)
+    w12, wt12 = [rf(2 * I, d, std=0.05) for _ in range(12)], [E(d, 2 * I) for _ in range(12)]
+    jobs = torch.zeros(12, 3, dtype=torch.int64)
+    for k in range(12):
+        jobs[k, 0], jobs[k, 1], jobs[k, 2] = w12[k].data_ptr(), wt12[k].data_ptr(), (2 * I) | (d << 32)
+    jobs, tiles = jobs.to(dev), ((2 * I + 63) // 64) * ((d + 63) // 64)
+    assert L0.cx_cast_f32_to_bf16(P(w32), P(wbf), w32.numel(), s) == 0
+    wbf0 = wbf.clone()
+    Wb = 4.0 * w32.numel()
+    # pooling and rotary: sequences of 128 tokens
+    Bq = T // 128
+    cu = torch.arange(0, (Bq + 1) * 128, 128, dtype=i32, device=dev)
+    emb, norm, demb, dh = E(Bq, d, dt=f32), E(Bq, dt=f32), rf(Bq, d), E(T, d)
+    assert L0.cx_pool_normalize_fwd(P(x), P(cu), P(emb), P(norm), Bq, d, 0, 1, s) == 0
+    emb0, norm0 = emb.clone(), norm.clone()
+    inv = 1.0 / (1000.0 ** (torch.arange(0, 64, 2, dtype=f32) / 64))
+    fr = torch.outer(torch.arange(128, dtype=f32), inv)
+    cos, sin = torch.cos(fr).to(dev).contiguous(), torch.sin(fr).to(dev).contiguous()
+    qkv0 = rn(T, 3 * d, std=0.5)
+    qkv = qkv0.clone()
+    # EVA-02: sequences of 1 + 256 tokens, 2-D rotary tables of 256 rows; SwiGLU + sub-LayerNorm at I
+    Be = T // 257
+    Te = Be * 257
+    cu_e = torch.arange(0, (Be + 1) * 257, 257, dtype=i32, device=dev)
+    cs2, sn2 = torch.cos(rf(256, 32)).contiguous(), torch.sin(rf(256, 32)).contiguous()
+    gam, bet = 1 + rf(I, std=0.1), rf(I, std=0.1)
+    g_o, a_o, z_o, mean, rstd = E(T, I), E(T, I), E(T, I), E(T, dt=f32), E(T, dt=f32)
+    assert L0.cx_swiglu_subln_fwd(P(yg), P(gam), P(bet), P(g_o), P(a_o), P(z_o), P(mean), P(rstd), T, I, 1e-6, s) == 0
+    sa, sg, sm, sr = a_o.clone(), g_o.clone(), mean.clone(), rstd.clone()
+    dgam, dbet, dbias = E(I, dt=f32), E(I, dt=f32), E(2 * I, dt=f32)
+    ws = E(1024 * 4 * I, dt=f32)
+    # ViT-B/16 front end: 224 x 224 images, 196 patches of 768 features
+    Bv = max(T // 256, 1)
+    pix, patches = rf(Bv, 3, 224, 224), E(Bv * 196, 768)
+    proj, cls, pos, seq = rn(Bv * 196, d), rf(d), rf(197, d), E(Bv * 197, d)
+    dzv, dproj, gcls, gpos = rn(Bv * 197, d), E(Bv * 196, d), E(d, dt=f32), E(197, d, dt=f32)
+    # cross-entropy: T / 8 rows of the MLM vocabulary
+    N, V = max(T // 8, 1), 30528
+    logits, labels = rn(N, V, std=2.0), torch.randint(0, V, (N,), device=dev, generator=g)
+    labels[::7] = -100
+    loss, lse, dloss, dlogits = E(N, dt=f32), E(N, dt=f32), rf(N), E(N, V)
+    assert L0.cx_xent_fwd(P(logits), 1, P(labels), P(loss), P(lse), N, V, V, 1.0, -100, s) == 0
+    lse0 = lse.clone()
+    # optimizer: the 136.7 M parameters of nomic-bert-2048 (+ 3: the scalar tail runs)
+    n = 136_700_003
+    p0, gr, m0, v0 = rf(n, std=0.05), rf(n, std=0.01), rf(n, std=3e-3), rf(n, std=0.01) ** 2
+    pw, mw, vw, ema = p0.clone(), m0.clone(), v0.clone(), p0.clone()
+    sq = torch.zeros(1, dtype=torch.float64, device=dev)
+    assert L0.cx_grad_sq_norm(P(gr), n, P(sq), s) == 0
+    sq_acc = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    def restore(*pairs):
+        return lambda: [dst.copy_(src) for dst, src in pairs]
+
+    return {
+        "swiglu_fwd_ew": (3 * Bt, [o_I], lambda L: L.cx_swiglu_fwd(P(yg), P(o_I), T, I, 1, s)),
+        "swiglu_bwd_ew": (5 * Bt, [dyg], lambda L: L.cx_swiglu_bwd(P(dact), P(yg), P(dyg), T, I, 1, s)),
+        "swiglu_bwd_gate_ew": (5 * Bt, [dyg], lambda L: L.cx_swiglu_bwd_gate(P(dact), P(act), P(gate), P(dyg), T, I, s)),
+        "bias_gelu_fwd": (2 * Bt, [o_I], lambda L: L.cx_bias_act_fwd(P(pre), P(bias), P(o_I), T, I, 0, s)),
+        "bias_qgelu_fwd": (2 * Bt, [o_I], lambda L: L.cx_bias_act_fwd(P(pre), P(bias), P(o_I), T, I, 1, s)),
+        "bias_gelu_bwd": (3 * Bt, [o_I], lambda L: L.cx_bias_gelu_bwd(P(dact), P(pre), P(bias), P(o_I), T, I, s)),
+        "bias_gelu_bwd_colsum": (3 * Bt, [o_I], lambda L: L.cx_bias_act_bwd_colsum(P(dact), P(pre), P(bias), P(o_I), P(dbet), T, I, 0, s)),
+        "bias_qgelu_bwd_colsum": (3 * Bt, [o_I], lambda L: L.cx_bias_act_bwd_colsum(P(dact), P(pre), P(bias), P(o_I), P(dbet), T, I, 1, s)),
+        "bias_grad": (Bt, [], lambda L: L.cx_bias_grad(P(dact), P(dbet), T, I, I, s)),
+        "cast_f32_bf16": (1.5 * Wb, [wbf], lambda L: L.cx_cast_f32_to_bf16(P(w32), P(wbf), w32.numel(), s)),
+        "cast_bf16_f32": (1.5 * Wb, [w_back], lambda L: L.cx_cast_bf16_to_f32(P(wbf0), P(w_back), w32.numel(), s)),
+        "cast_transpose": (1.5 * Wb, [wt], lambda L: L.cx_cast_transpose_f32_to_bf16(P(w32), P(wt), 2 * I, d, s)),
+        "cast_transpose_x12": (18 * Wb, wt12, lambda L: L.cx_cast_transpose_f32_to_bf16_batched(P(jobs), 12, tiles, s)),
+        "transpose_bf16": (2 * Bd, [xt], lambda L: L.cx_transpose_bf16(P(x), P(xt), T, d, d, T, T, s)),
+        "transpose_f32": (2 * Wb, [wt32], lambda L: L.cx_transpose_f32(P(w32), P(wt32), 2 * I, d, d, 2 * I, s)),
+        "pool_fwd": (Bd, [emb, norm], lambda L: L.cx_pool_normalize_fwd(P(x), P(cu), P(emb), P(norm), Bq, d, 0, 1, s)),
+        "pool_bwd": (Bd, [dh], lambda L: L.cx_pool_normalize_bwd(P(demb), P(emb0), P(norm0), P(cu), P(dh), Bq, d, 0, 1, s)),
+        "rotary_qkv": (4 * Bd, [qkv], lambda L: L.cx_rotary_qkv_inplace(P(qkv), P(cu), P(cos), P(sin), Bq, H, T, 128, 1, s), restore((qkv, qkv0))),
+        "rope2d_qkv": (4 * Bd, [qkv], lambda L: L.cx_rope2d_qkv_inplace(P(qkv), P(cu_e), P(cs2), P(sn2), 256, Be, H, Te, 1, 1, s), restore((qkv, qkv0))),
+        "swiglu_subln_fwd": (5 * Bt, [g_o, a_o, z_o, mean, rstd], lambda L: L.cx_swiglu_subln_fwd(P(yg), P(gam), P(bet), P(g_o), P(a_o), P(z_o), P(mean), P(rstd), T, I, 1e-6, s)),
+        "swiglu_subln_bwd": (5 * Bt, [dyg, dgam, dbet, dbias], lambda L: L.cx_swiglu_subln_bwd(P(dact), P(sa), P(sg), P(sm), P(sr), P(gam), P(dyg), P(dgam), P(dbet), P(dbias), P(ws), ws.numel(), T, I, s)),
+        "vit_patchify": (6.0 * pix.numel(), [patches], lambda L: L.cx_vit_patchify(P(pix), 0, P(patches), Bv, 3, 224, 224, 16, s)),
+        "vit_assemble_fwd": (4.0 * proj.numel(), [seq], lambda L: L.cx_vit_assemble_fwd(P(proj), P(cls), P(pos), P(seq), Bv, 196, d, s)),
+        "vit_assemble_bwd": (4.0 * dzv.numel(), [dproj, gcls, gpos], lambda L: L.cx_vit_assemble_bwd(P(dzv), P(dproj), P(gcls), P(gpos), Bv, 196, d, s)),
+        "xent_fwd": (2.0 * N * V, [loss, lse], lambda L: L.cx_xent_fwd(P(logits), 1, P(labels), P(loss), P(lse), N, V, V, 1.0, -100, s)),
+        "xent_bwd": (4.0 * N * V, [dlogits], lambda L: L.cx_xent_bwd(P(dloss), P(logits), 1, P(lse0), P(labels), P(dlogits), N, V, V, V, 1.0, -100, s)),
+        "adamw_clip_step": (28.0 * n, [pw, mw, vw], lambda L: L.cx_adamw_clip_step(P(pw), P(gr), P(mw), P(vw), n, 2e-4, 0.9, 0.999, 1e-8, 0.1, 1000, P(sq), 1.0, s),
+                            restore((pw, p0), (mw, m0), (vw, v0))),
+        "ema_update": (12.0 * n, [ema], lambda L: L.cx_ema_update(P(ema), P(pw), n, 0.999, s), restore((ema, p0), (pw, p0))),
+        "grad_sq_norm": (4.0 * n, [], lambda L: L.cx_grad_sq_norm(P(gr), n, P(sq_acc), s)),
+    }
+
+
+GLUE = ("swiglu_fwd_ew", "swiglu_bwd_ew", "swiglu_bwd_gate_ew", "bias_gelu_fwd", "bias_qgelu_fwd", "bias_gelu_bwd", "bias_gelu_bwd_colsum",
+        "bias_qgelu_bwd_colsum", "bias_grad", "cast_f32_bf16", "cast_bf16_f32", "cast_transpose", "cast_transpose_x12", "transpose_bf16",
+        "transpose_f32", "pool_fwd", "pool_bwd", "rotary_qkv", "rope2d_qkv", "swiglu_subln_fwd", "swiglu_subln_bwd", "vit_patchify",
+        "vit_assemble_fwd", "vit_assemble_bwd", "xent_fwd", "xent_bwd", "adamw_clip_step", "ema_update", "grad_sq_norm")
+GROUPS = {glue_cases: GLUE, gemm_cases: ("swiglu_bwd", "swiglu_fwd_save", "swiglu_fwd", "qkv_fwd", "out_dgrad", "out_fwd_res", "fc2_fwd_res", "qkv_dgrad_res", "fc1_dgrad_res"),
           attn_cases: ("attn_fwd", "attn_bwd", "attn_bwd_dpre", "attn_bwd_drop", "attn_fwd_drop", "attn_bwd_ragged"),
           ln_cases: ("ln_fwd", "ln_fwd_res_z", "ln_bwd_ws", "ln_bwd_colsum_ws", "ln_bwd_atomics", "ln_pooled_ws", "ln_drop_fwd", "ln_drop_bwd_colsum_ws",
                      "ln_mixed_fwd_f32", "ln_mixed_bwd_f32", "embed_fwd", "embed_bwd_sorted", "dropout_scale")}
 want = [c for c in a.cases.split(",") if c] or [c for grp in GROUPS.values() for c in grp]
+want = [c for w in want for c in (GLUE if w == "glue" else (w,))]
 unknown = [c for c in want if not any(c in grp for grp in GROUPS.values())]
 assert not unknown, f"unknown cases {unknown}"
 cases = {}
@@ -197,8 +304,8 @@ for cname in want:
             ref = got
         else:
             same = all(torch.equal(x_.view(torch.uint8), y_.view(torch.uint8)) for x_, y_ in zip(got, ref))
-            rel = max(float((x_.float() - y_.float()).norm() / (y_.float().norm() + 1e-30)) for x_, y_ in zip(got, ref))
-            diffs[n] = "bit-ident" if same else f"{rel:.2e}"
+            rel = max((float((x_.float() - y_.float()).norm() / (y_.float().norm() + 1e-30)) for x_, y_ in zip(got, ref)), default=0.0)
+            diffs[n] = "timed only" if not outs else "bit-ident" if same else f"{rel:.2e}"
     t = {n: [] for n in names}
     for _ in range(a.rounds):
         for n in names:

@@ -1,12 +1,13 @@
-"""fp64 and bit-exact references of the HBM-bound glue kernels (contrastors_amd/csrc/elementwise.hip, xent.hip, optimizer.hip),
-the seeded inputs of their edge tests, fp32 emulations of the kernels' own formulas, poisoned slabs and the checkers they share.
+"""fp64 and bit-exact references of the HBM-bound glue kernels (contrastors_amd/csrc/elementwise.hip, xent.hip, optimizer.hip, the
+front end of vit.hip), the seeded inputs of their edge tests, fp32 emulations of the kernels' own formulas, poisoned slabs and the checkers they share.
 Plain torch, any device: tests/test_ew_ref_cpu.py proves this file against fp64 autograd, measures the constants below and plants
 errors; tests/test_elementwise_edges_gpu.py and tests/test_xent_optimizer_edges_gpu.py hold the kernels to it.  What exists is reused:
 bf16_ulp / bf16_round / bits / check_rows (tests/ln_ref.py), the activation formulas, layouts, check_bits, check_poison and meas_ratio
 (tests/gemm_ref.py), rotate_bf16 / rotary_tables (tests/attn_ref.py).
 
 Bit-exact operations (no tolerance): cx_transpose_bf16, cx_transpose_f32, cx_cast_bf16_to_f32, cx_cast_f32_to_bf16,
-cx_cast_transpose_f32_to_bf16 and its batched form, cx_rotary_qkv_inplace and cx_rotary_apply.  The cast reference is torch's CPU
+cx_cast_transpose_f32_to_bf16 and its batched form, cx_rotary_qkv_inplace and cx_rotary_apply, and the three front-end kernels of
+vit.hip (they move data, do at most one fp32 add per element or a short fp32 sum in a fixed order, and round to bf16 once).  The cast reference is torch's CPU
 `.to(torch.bfloat16)` (round to nearest, ties to even); cast_inputs() holds exact ties of both parities, the two fp32 neighbours of a
 tie, +-0, +-inf, NaN (compared with isnan, not by payload) and +-float32 max (rounds to inf).  It holds NO fp32 subnormals: the
 denormal mode of the hardware conversion is not a contract of this project.
@@ -18,7 +19,7 @@ C = 4 C_MEAS[family][form].  C_MEAS is the worst |emulation - ref| / (2^-24 T) o
 (the emu_* functions below: exp2 of the argument times log2 e, the reciprocal, the A&S 7.1.26 erf polynomial, the kernels' summation
 order where it is long) on exactly the inputs the tests use, measured and asserted by test_ew_ref_cpu.py::test_measured_constants,
 never against a kernel.  The factor 4 is the project's stated margin: the two 1-ulp hardware approximations v_exp_f32 and v_rcp_f32
-(elementwise.hip: sigmoidf_), the erf polynomial's 1.5e-7 and FMA contraction.  The saturation family (exact 0, +- the smallest bf16
+(cx_common.h: sigmoid_fast), the erf polynomial's 1.5e-7 and FMA contraction.  The saturation family (exact 0, +- the smallest bf16
 normal, +-2^-20, +-8, +-20, +-50, +-100 as gate or pre-activation) has its own row: its constants are larger than the Gaussian ones
 because T holds no term for the fp32 rounding of the exponent's argument log2(e) g, which reaches sigmoid(g) times |g| where the
 exponential dominates (g = -50: about 50 2^-24 relative); at +-100 exp2 over- and underflows, the reciprocal sees inf, and the result
@@ -721,3 +722,76 @@ def ema_step(ema, p, decay, dtype=F64, swapped=False):
         dk, w = w, dk
     a, b = dk * ema.to(dtype), w * p.to(dtype)
     return a + b, a.abs() + b.abs()
+
+
+# ====================================================================================== ViT front end (vit.hip): bit-exact
+VIT_PATCHIFY = ((2, 3, 8, 12, 4), (3, 3, 32, 48, 16))     # (B, C, H, W, patch): 144 lanes = one partial block; 3456 = 13.5 blocks
+VIT_ASSEMBLE = ((3, 6, 24), (2, 6, 520))                 # (B, P, d)
+# K = 4 of 6 patches per image, unsorted, the last patch in each; patch 4 is dropped by every image
+VIT_P_ALL, VIT_KEEP = 6, ((5, 0, 3, 2), (1, 5, 2, 0), (2, 3, 5, 1))
+
+
+def vit_keep(B):
+    return torch.tensor(VIT_KEEP[:B], dtype=torch.int32)
+
+
+def vit_inv(keep, P_all):
+    """inv[b][patch] = position of `patch` among image b's kept ones, or -1 (what cx_vit_assemble_bwd_gather reads)."""
+    inv = torch.full((keep.shape[0], P_all), -1, dtype=torch.int32)
+    for b, row in enumerate(keep.tolist()):
+        for j, pi in enumerate(row):
+            inv[b, pi] = j
+    return inv
+
+
+def vit_dz(B, P, d, seed):
+    """dz (B (P + 1), d) bf16 for the assembly backward: Gaussian, image b scaled by 2^20, 1, 1/2, ... so that the fp32 sum over the
+    images rounds after each addition and their ORDER shows in the result (three bf16 values of one magnitude add exactly)."""
+    z = R.gauss_bf16(B * (P + 1), d, seed).reshape(B, P + 1, d).float()
+    scale = torch.tensor([2.0 ** 20] + [2.0 ** -i for i in range(B - 1)])
+    return (z * scale[:, None, None]).to(BF).reshape(B * (P + 1), d)
+
+
+def patchify_ref(pix, patch, keep=None):
+    """pixels (B, C, H, W) -> (B * hp * wp, C * patch * patch) bf16: "b c (h p1) (w p2) -> b h w (c p1 p2)", then round to nearest even.
+    keep (B, K): row b * K + j is patch keep[b][j]."""
+    B, C, H, W = pix.shape
+    hp, wp = H // patch, W // patch
+    x = pix.reshape(B, C, hp, patch, wp, patch).permute(0, 2, 4, 1, 3, 5).reshape(B, hp * wp, C * patch * patch)
+    if keep is not None:
+        x = torch.stack([x[b, keep[b].long()] for b in range(B)])
+    return x.reshape(-1, C * patch * patch).float().to(BF)
+
+
+def assemble_fwd_ref(proj, cls, pos, B, P, keep=None):
+    """out[b, 0] = bf16(cls + pos[0]); out[b, s] = bf16(float(proj[b P + s - 1]) + pos[s]) -- pos[1 + keep[b][s - 1]] with keep; one fp32
+    add per element.  -> (B (P + 1), d) bf16."""
+    d = proj.shape[1]
+    out = torch.empty(B, P + 1, d, dtype=F32)
+    out[:, 0] = cls + pos[0]
+    for b in range(B):
+        rows = torch.arange(1, P + 1) if keep is None else 1 + keep[b].long()
+        out[b, 1:] = proj[b * P:(b + 1) * P].float() + pos[rows]
+    return out.reshape(B * (P + 1), d).to(BF)
+
+
+def assemble_bwd_ref(dz, B, P, gpos0, gcls0, dproj0, inv=None):
+    """dproj[b P + sk - 1] = dz[b, sk] (a copy) and gpos[s] = gpos0[s] + (((0 + dz[0, .]) + dz[1, .]) + ...) in fp32, images in order, the
+    kernel's order; gcls likewise from position 0.  With inv (B, P_all) the sum of original position s >= 1 takes image b's row
+    sk = 1 + inv[b][s - 1] and skips the images that dropped the patch; rows of dproj0 that nothing maps to come back as they were.
+    -> dproj, gpos, gcls"""
+    d = dz.shape[1]
+    z = dz.reshape(B, P + 1, d)
+    n_pos = gpos0.shape[0]
+    dproj, acc = dproj0.clone().reshape(B, P, d), torch.zeros(n_pos, d, dtype=F32)
+    for b in range(B):
+        for s in range(n_pos):
+            sk = s
+            if inv is not None and s > 0:
+                if int(inv[b, s - 1]) < 0:
+                    continue
+                sk = 1 + int(inv[b, s - 1])
+            if s > 0:
+                dproj[b, sk - 1] = z[b, sk]
+            acc[s] = acc[s] + z[b, sk].float()
+    return dproj.reshape(B * P, d), gpos0 + acc, gcls0 + acc[0]

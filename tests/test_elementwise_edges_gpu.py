@@ -1,7 +1,7 @@
-"""The glue kernels of contrastors_amd/csrc/elementwise.hip through the C ABI against tests/ew_ref.py, per element, at the grid, tail,
-width and stride edges of their launchers.
+"""The glue kernels of contrastors_amd/csrc/elementwise.hip and the front end of vit.hip through the C ABI against tests/ew_ref.py, per
+element, at the grid, tail, width and stride edges of their launchers.
 
-Transposes, casts and both rotary entry points are compared BIT FOR BIT (the cast with torch's CPU conversion on inputs full of exact
+Transposes, casts, both rotary entry points and the three ViT front-end kernels are compared BIT FOR BIT (the cast with torch's CPU conversion on inputs full of exact
 ties, the rotary with attn_ref.rotate_bf16).  Activations, pooling and the fused activation backward are held per element to the fp64
 formula on the exact rounded inputs under 1 ulp_bf16(ref) + C 2^-24 T (bf16 results) or C 2^-24 T (fp32 results), C = 4 C_meas with
 C_meas measured by tests/test_ew_ref_cpu.py on an fp32 emulation of the kernels' formulas (never against a kernel), on Gaussian inputs
@@ -38,6 +38,13 @@ Which test reaches what (by reading the launchers):
        200-token sequence on 16 384 lanes), an empty and a one-token sequence, sign +-1 ....... test_rotary_qkv
     rotary_kernel nwhich = 1: tok_stride = H 64, 3 H 64, H 64 + 8; max_seqlen below the longest
        sequence (gx from max_seqlen, the stride loop covers the rest); CX_ERR_ALIGN / _ARG ..... test_rotary_apply
+    patchify_kernel<float / bf16>: one partial block (144 lanes), 13.5 blocks; every patch, or
+       4 of 6 gathered in unsorted order, the last patch among them ........................... test_vit_patchify
+    vit_assemble_fwd_kernel: 9 and 65 lanes of the last block idle; position rows by sequence
+       slot, or by kept patch .................................................................. test_vit_assemble_fwd
+    vit_assemble_bwd_kernel: a block of 3 lanes (d = 24), two column blocks with 63 lanes of the
+       second idle (d = 520); every position, or the original positions through `inv` (-1 entries,
+       a patch no image kept, a slot nothing maps to); += on non-zero gpos / gcls; either NULL .. test_vit_assemble_bwd
 """
 import numpy as np
 import pytest
@@ -374,3 +381,79 @@ def test_rotary_apply(stride, max_seqlen):
     assert L().cx_rotary_apply(X.ptr, tok, None, COS.ptr, SIN.ptr, B, H, T, max_seqlen, 1, S()) == ERR_ARG
     assert R.check_bits("rotary_apply: a rejected call writes nothing", X.get(), ref) == 0
     report("cx_rotary_apply", test=f"stride={stride} max_seqlen={max_seqlen}", differing=0)
+
+
+# ====================================================================================================== ViT front end
+@pytest.mark.parametrize("gather", [False, True])
+@pytest.mark.parametrize("dtype", [F32, BF])
+@pytest.mark.parametrize("B,C,H,W,p", E.VIT_PATCHIFY)
+def test_vit_patchify(B, C, H, W, p, dtype, gather):
+    pix = E.cast_inputs(B * C * H * W, 140 + B).reshape(B, C, H, W)           # exact ties, +-0, inf and a NaN among the pixels
+    if dtype == BF:
+        pix = E.cast_ref(pix)
+    keep = E.vit_keep(B) if gather else None
+    rows = B * (keep.shape[1] if gather else E.VIT_P_ALL)
+    X, O = slab(B * C * H, W, dtype=dtype, data=pix, name="pixels"), slab(rows, C * p * p, name="patches")
+    kd = keep.to(DEV) if gather else None
+    if gather:
+        rc = L().cx_vit_patchify_gather(X.ptr, int(dtype == BF), O.ptr, B, C, H, W, p, kd.data_ptr(), keep.shape[1], S())
+    else:
+        rc = L().cx_vit_patchify(X.ptr, int(dtype == BF), O.ptr, B, C, H, W, p, S())
+    _C.check(rc, "vit_patchify")
+    assert E.check_bits_nan(f"patchify {B}x{C}x{H}x{W} p={p} gather={gather}", O.get(), E.patchify_ref(pix, p, keep)) == 0
+    report("cx_vit_patchify_gather" if gather else "cx_vit_patchify", test=f"{H}x{W} p={p} {dtype}", differing=0)
+
+
+@pytest.mark.parametrize("gather", [False, True])
+@pytest.mark.parametrize("B,P_all,d", E.VIT_ASSEMBLE)
+def test_vit_assemble_fwd(B, P_all, d, gather):
+    keep = E.vit_keep(B) if gather else None
+    P = keep.shape[1] if gather else P_all
+    proj = R.gauss_bf16(B * P, d, 150 + d)
+    cls, pos = torch.randn(d, generator=E._gen(151)), torch.randn(P_all + 1, d, generator=E._gen(152))
+    X, CLS, POS = slab(B * P, d, data=proj, name="proj"), slab(1, d, dtype=F32, data=cls, name="cls"), slab(P_all + 1, d, dtype=F32, data=pos, name="pos")
+    O = slab(B * (P + 1), d, name="out")
+    kd = keep.to(DEV) if gather else None
+    if gather:
+        rc = L().cx_vit_assemble_fwd_gather(X.ptr, CLS.ptr, POS.ptr, O.ptr, B, P, d, kd.data_ptr(), S())
+    else:
+        rc = L().cx_vit_assemble_fwd(X.ptr, CLS.ptr, POS.ptr, O.ptr, B, P, d, S())
+    _C.check(rc, "vit_assemble_fwd")
+    assert R.check_bits(f"assemble_fwd B={B} P={P} d={d} gather={gather}", O.get(), E.assemble_fwd_ref(proj, cls, pos, B, P, keep)) == 0
+    report("cx_vit_assemble_fwd_gather" if gather else "cx_vit_assemble_fwd", test=f"B={B} d={d}", differing=0)
+
+
+@pytest.mark.parametrize("mode", ["plain", "inv", "no_gpos", "no_gcls"])
+@pytest.mark.parametrize("d", [24, 520])
+def test_vit_assemble_bwd(d, mode):
+    B, P_all = 3, E.VIT_P_ALL
+    inv = None
+    if mode == "inv":
+        inv = E.vit_inv(E.vit_keep(B), P_all)
+        inv[2, 1] = -1                      # image 2 loses slot 3 (patch 1): dproj row 2 K + 3 is never written and stays poison
+    Pk = 4 if mode == "inv" else P_all   # patches per image in dz / dproj
+    dz = E.vit_dz(B, Pk, d, 160 + d)
+    gpos0, gcls0 = torch.randn(P_all + 1, d, generator=E._gen(161)), torch.randn(d, generator=E._gen(162))
+    Z, DP = slab(B * (Pk + 1), d, data=dz, name="dz"), slab(B * Pk, d, name="dproj")
+    GP = None if mode == "no_gpos" else slab(P_all + 1, d, dtype=F32, data=gpos0, name="gpos")
+    GC = None if mode == "no_gcls" else slab(1, d, dtype=F32, data=gcls0, name="gcls")
+    if inv is not None:
+        iv = inv.to(DEV)
+        rc = L().cx_vit_assemble_bwd_gather(Z.ptr, DP.ptr, P(GC), P(GP), B, Pk, d, iv.data_ptr(), P_all, S())
+    else:
+        rc = L().cx_vit_assemble_bwd(Z.ptr, DP.ptr, P(GC), P(GP), B, Pk, d, S())
+    _C.check(rc, "vit_assemble_bwd")
+    dproj, gpos, gcls = E.assemble_bwd_ref(dz, B, Pk, gpos0, gcls0, torch.zeros(B * Pk, d, dtype=BF), inv)
+    got = DP.get()
+    if inv is not None:                     # the row nothing maps to: still the slab's poison
+        hole = 2 * Pk + 3
+        assert bool(torch.isnan(got[hole]).all())
+        got[hole] = 0.0
+    assert R.check_bits(f"assemble_bwd dproj d={d} {mode}", got, dproj) == 0
+    if GP is not None:
+        assert R.check_bits(f"assemble_bwd gpos d={d} {mode}", GP.get(), gpos) == 0
+        if inv is not None:
+            assert R.check_bits("gpos of the patch no image kept", GP.get()[5:6], gpos0[5:6]) == 0
+    if GC is not None:
+        assert R.check_bits(f"assemble_bwd gcls d={d} {mode}", GC.get(), gcls[None]) == 0
+    report("cx_vit_assemble_bwd_gather" if inv is not None else "cx_vit_assemble_bwd", test=f"d={d} {mode}", differing=0)

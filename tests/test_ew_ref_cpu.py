@@ -107,6 +107,71 @@ def test_planted_rotary_sign_and_truncating_cast_are_rejected():
     rejected(BitMismatch, lambda: E.check_bits_nan("cast", nan_lost[None], E.cast_ref(x32)[None]), row=0, col=7)
 
 
+# ====================================================================================================== ViT front end
+def test_vit_patchify_reference_equals_index_arithmetic():
+    B, C, H, W, p = E.VIT_PATCHIFY[0]
+    pix = E.cast_inputs(B * C * H * W, 31).reshape(B, C, H, W)
+    keep = E.vit_keep(B)
+    wp, P = W // p, (H // p) * (W // p)
+    assert P == E.VIT_P_ALL and all(sorted(k) != list(k) and E.VIT_P_ALL - 1 in k for k in E.VIT_KEEP)
+    for kp in (None, keep):
+        ref = E.patchify_ref(pix, p, kp)
+        rows = P if kp is None else kp.shape[1]
+        assert tuple(ref.shape) == (B * rows, C * p * p)
+        want = torch.empty(B * rows, C * p * p, dtype=F32)
+        for b in range(B):
+            for j in range(rows):
+                pi = j if kp is None else int(kp[b, j])
+                ph, pw = divmod(pi, wp)
+                for c in range(C):
+                    for p1 in range(p):
+                        for p2 in range(p):
+                            want[b * rows + j, (c * p + p1) * p + p2] = pix[b, c, ph * p + p1, pw * p + p2]
+        assert E.check_bits_nan("patchify", ref, E.cast_ref(want)) == 0
+    bf = E.cast_ref(pix)                                                     # bf16 pixels: the rearrangement alone
+    assert E.check_bits_nan("patchify bf16", E.patchify_ref(bf, p), E.patchify_ref(pix, p)) == 0
+    r, c = rejected(BitMismatch, lambda: E.check_bits_nan("patchify", E.patchify_ref(pix, p, keep.flip(1)), E.patchify_ref(pix, p, keep)))
+    assert r == 0
+
+
+def test_vit_assemble_references_restated_and_planted_errors_are_rejected():
+    B, P_all, d = 3, E.VIT_P_ALL, 24
+    keep = E.vit_keep(B)
+    K = keep.shape[1]
+    inv = E.vit_inv(keep, P_all)
+    assert sorted(int(inv[b, pi]) for b in range(B) for pi in keep[b].tolist()) == sorted(list(range(K)) * B)
+    assert bool((inv[:, 4] < 0).all())                                        # patch 4: dropped by every image
+    cls, pos = torch.randn(d, generator=E._gen(41)), torch.randn(P_all + 1, d, generator=E._gen(42))
+    for kp, P in ((None, P_all), (keep, K)):
+        proj = R.gauss_bf16(B * P, d, 43)
+        ref = E.assemble_fwd_ref(proj, cls, pos, B, P, kp).reshape(B, P + 1, d)
+        for b in range(B):
+            assert torch.equal(ref[b, 0], (cls + pos[0]).to(BF))
+            for s in range(1, P + 1):
+                ps = s if kp is None else 1 + int(kp[b, s - 1])
+                assert torch.equal(ref[b, s], (proj[b * P + s - 1].float() + pos[ps]).to(BF)), (b, s)
+    # planted: the position row of the kept SLOT instead of the kept PATCH
+    proj = R.gauss_bf16(B * K, d, 43)
+    rejected(BitMismatch, lambda: R.check_bits("assemble_fwd", E.assemble_fwd_ref(proj, cls, pos, B, K, None), E.assemble_fwd_ref(proj, cls, pos, B, K, keep)), row=1)
+    # backward: every dz row lands once; the sums in the images' order; an untouched row stays what it was
+    gpos0, gcls0 = torch.randn(P_all + 1, d, generator=E._gen(44)), torch.randn(d, generator=E._gen(45))
+    dz = E.vit_dz(B, K, d, 46)
+    hole = inv.clone()
+    hole[2, 1] = -1                                                          # image 2 loses its slot 3 (patch 1): dproj row 2 K + 3 is never written
+    poison = torch.full((B * K, d), float("nan"), dtype=BF)
+    dproj, gpos, gcls = E.assemble_bwd_ref(dz, B, K, gpos0, gcls0, poison, hole)
+    z = dz.reshape(B, K + 1, d)
+    assert bool(torch.isnan(dproj[2 * K + 3]).all()) and int(torch.isnan(dproj).any(1).sum()) == 1
+    assert torch.equal(dproj.reshape(B, K, d)[:2], z[:2, 1:]) and torch.equal(dproj.reshape(B, K, d)[2, :3], z[2, 1:4])
+    assert torch.equal(gpos[5], gpos0[5]) and torch.equal(gcls, gcls0 + ((z[0, 0].float() + z[1, 0].float()) + z[2, 0].float()))
+    assert torch.equal(gpos[1], gpos0[1] + (z[0, 2].float() + z[1, 4].float()))             # patch 0: slot 1 of image 0, slot 3 of image 1
+    dproj_p, gpos_p, _ = E.assemble_bwd_ref(dz[:B * (K + 1)], B, K, gpos0[:K + 1], gcls0, poison, None)
+    assert torch.equal(dproj_p.reshape(B, K, d), z[:, 1:]) and torch.equal(gpos_p[2], gpos0[2] + ((z[0, 2].float() + z[1, 2].float()) + z[2, 2].float()))
+    # planted: the batch summed in the reverse order (vit_dz makes the order visible)
+    rev = gpos0[0] + ((z[2, 0].float() + z[1, 0].float()) + z[0, 0].float())
+    rejected(BitMismatch, lambda: R.check_bits("gpos order", rev[None], gpos[0][None]), row=0)
+
+
 # ======================================================================================================== activations
 def _act_floors(inp, bias):
     """form -> the fp32 underflow term of its bound (ew_ref.act_floor)."""
