@@ -188,6 +188,13 @@ _SIGS = {
     "cx_search_hamming_ws_bytes": (i64, [i32, i64, i32, i32]),
     "cx_search_hamming_topk": (i32, [vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "cx_rescore_topk": (i32, [vp, vp, vp, vp, i32, i64, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
+    "cx_embed_ln_fwd_typed": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
+    "cx_embed_ln_bwd_typed": (i32, [vp] * 7 + [i32] + [vp] * 10 + [i64, i32, i32, i32, i32, vp]),
+    "cx_embed_ln_bwd_sorted_typed": (i32, [vp] * 7 + [i32] + [vp] * 10 + [i64, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "cx_seqcls_ws_floats": (i64, [i32, i32, i32]),
+    "cx_seqcls_head_fwd": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, f32, u64, u64, vp, vp, vp, i32, i32, i32, vp]),
+    "cx_seqcls_head_bwd": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, f32, f32, u64, u64, vp, i64, vp, vp, vp, vp, vp, i32, i32,
+                                 i32, vp]),
     "cx_simkl_ws_floats": (i64, [i32, i32]),
     "cx_simkl_fwd": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cx_simkl_bwd": (i32, [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
@@ -199,6 +206,10 @@ _SIGS = {
     "cx_transpose_f32": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "cx_encoder_forward": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, vp, vp, i32, i32, i32,
                                  i32, i32, vp, vp]),
+    "cx_encoder_forward_typed": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, vp, vp, vp, i32, i32, i32,
+                                       i32, i32, vp, vp]),
+    "cx_encoder_backward_typed": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, vp, vp, vp, i32, i32, i32,
+                                        i32, vp, vp, vp, vp, vp]),
     "cx_encoder_forward_hidden": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, vp, vp, i32, i32, i32,
                                         i32, i32, vp, vp]),
     "cx_encoder_backward_hidden": (i32, [C.POINTER(CxEncoderDesc), C.POINTER(CxChunkBuffers), vp, vp, vp, i32, i32, i32,

@@ -105,6 +105,7 @@ class DataArgs(BaseModel):
     query_max_length: Optional[int] = None
     document_max_length: Optional[int] = None
     mlm_prob: Optional[float] = None
+    task_name: Optional[str] = None   # model_type: glue (sc/trainers/glue.py:50): cola, mnli, mrpc, qnli, qqp, rte, sst2, stsb
 
 
 class ModelArgs(BaseModel):

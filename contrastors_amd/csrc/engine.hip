@@ -645,20 +645,24 @@ int vit_backward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const
     CX_TRY(wgrad(buf->patch_proj, d, buf->patch_in, enc->patch_dim, enc->gWpatch, buf, Tp, stream));
     return mark_grads_done(buf, enc->n_layer, stream);
 }
-}  // namespace
 
-extern "C" {
-
-int cx_encoder_forward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
-                       const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S, int T, int max_seqlen,
-                       int save_for_backward, float* emb_out, void* stream) {
+// The pooled text pair.  token_type_ids == NULL: every token takes row 0 of the type table through the untyped embedding
+// kernels (cx_encoder_forward / _backward); otherwise (Bc, S) int64 segment ids and enc->type_emb / gtype_emb are (2, d).
+int text_forward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                      const int64_t* token_type_ids, const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S, int T,
+                      int max_seqlen, int save_for_backward, float* emb_out, void* stream) {
     if (Bc <= 0 || T <= 0) return CX_OK;
     CX_TRY(check_desc(enc, buf, T));
     (void)hipGetLastError();  // a stale error of some earlier, unrelated runtime call must not fail this launch train
     const int d = enc->d, I = enc->d_inner;
     const Slots s = make_slots(enc, buf, save_for_backward);
-    CX_TRY(cx_embed_ln_fwd(input_ids, indices, enc->word_emb, enc->type_emb, enc->pos_emb, enc->emb_ln_g,
-                           enc->emb_ln_b, buf->h0, buf->emb_mean, buf->emb_rstd, T, S, d, enc->ln_eps, stream));
+    if (token_type_ids)
+        CX_TRY(cx_embed_ln_fwd_typed(input_ids, token_type_ids, indices, enc->word_emb, enc->type_emb, 2, enc->pos_emb,
+                                     enc->emb_ln_g, enc->emb_ln_b, buf->h0, buf->emb_mean, buf->emb_rstd, T, S, d, enc->ln_eps,
+                                     stream));
+    else
+        CX_TRY(cx_embed_ln_fwd(input_ids, indices, enc->word_emb, enc->type_emb, enc->pos_emb, enc->emb_ln_g,
+                               enc->emb_ln_b, buf->h0, buf->emb_mean, buf->emb_rstd, T, S, d, enc->ln_eps, stream));
     if (buf->drop_active && enc->embd_pdrop > 0.f)  // modeling_nomic_bert.py:534-535: dropout on the embedding-LN output
         CX_TRY(cx_dropout_scale(buf->h0, (long)T * d, enc->embd_pdrop, buf->drop_seed, buf->drop_offset, 2 * enc->n_layer, stream));
     const uint16_t* h_final = nullptr;
@@ -667,10 +671,10 @@ int cx_encoder_forward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, cons
                                  stream);
 }
 
-int cx_encoder_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
-                        const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S, int T, int max_seqlen,
-                        const float* demb, const float* emb_out, const int32_t* sort_ids, const int32_t* sort_perm,
-                        void* stream) {
+int text_backward_impl(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                       const int64_t* token_type_ids, const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S, int T,
+                       int max_seqlen, const float* demb, const float* emb_out, const int32_t* sort_ids,
+                       const int32_t* sort_perm, void* stream) {
     if (Bc <= 0 || T <= 0) return CX_OK;
     CX_TRY(check_desc(enc, buf, T));
     if (!demb || !emb_out) return CX_ERR_ARG;
@@ -698,7 +702,19 @@ int cx_encoder_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, con
     }
     // word rows: deterministic segmented reduction when the host supplied the sorted token order (g_wide is free by now:
     // (T, >= 3d) bf16 = room for the (T, d) fp32 row gradients), fp32 atomics otherwise
-    if (sort_ids && sort_perm) {
+    // (the typed forms fold both type rows' block partials through ws_f32, which no kernel is using by now)
+    if (token_type_ids && sort_ids && sort_perm) {
+        CX_TRY(cx_embed_ln_bwd_sorted_typed(da, db, input_ids, token_type_ids, indices, enc->word_emb, enc->type_emb, 2,
+                                            enc->pos_emb, enc->emb_ln_g, buf->emb_mean, buf->emb_rstd, enc->gword_emb,
+                                            enc->gtype_emb, enc->gpos_emb, enc->gemb_ln_g, enc->gemb_ln_b, buf->ws_f32,
+                                            buf->ws_floats, T, S, d, enc->padding_idx, enc->vocab, sort_ids, sort_perm,
+                                            reinterpret_cast<float*>(buf->g_wide), stream));
+    } else if (token_type_ids) {
+        CX_TRY(cx_embed_ln_bwd_typed(da, db, input_ids, token_type_ids, indices, enc->word_emb, enc->type_emb, 2, enc->pos_emb,
+                                     enc->emb_ln_g, buf->emb_mean, buf->emb_rstd, enc->gword_emb, enc->gtype_emb, enc->gpos_emb,
+                                     enc->gemb_ln_g, enc->gemb_ln_b, buf->ws_f32, buf->ws_floats, T, S, d, enc->padding_idx,
+                                     stream));
+    } else if (sort_ids && sort_perm) {
         CX_TRY(cx_embed_ln_bwd_sorted(da, db, input_ids, indices, enc->word_emb, enc->type_emb, enc->pos_emb, enc->emb_ln_g,
                                       buf->emb_mean, buf->emb_rstd, enc->gword_emb, enc->gtype_emb, enc->gpos_emb,
                                       enc->gemb_ln_g, enc->gemb_ln_b, T, S, d, enc->padding_idx, enc->vocab, sort_ids,
@@ -709,6 +725,37 @@ int cx_encoder_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, con
                                enc->gemb_ln_g, enc->gemb_ln_b, T, S, d, enc->padding_idx, stream));
     }
     return mark_grads_done(buf, enc->n_layer, stream);
+}
+}  // namespace
+
+extern "C" {
+
+int cx_encoder_forward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                       const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S, int T, int max_seqlen,
+                       int save_for_backward, float* emb_out, void* stream) {
+    return text_forward_impl(enc, buf, input_ids, nullptr, indices, cu_seqlens, Bc, S, T, max_seqlen, save_for_backward, emb_out,
+                             stream);
+}
+int cx_encoder_forward_typed(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                             const int64_t* token_type_ids, const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S,
+                             int T, int max_seqlen, int save_for_backward, float* emb_out, void* stream) {
+    return text_forward_impl(enc, buf, input_ids, token_type_ids, indices, cu_seqlens, Bc, S, T, max_seqlen, save_for_backward,
+                             emb_out, stream);
+}
+
+int cx_encoder_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                        const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S, int T, int max_seqlen,
+                        const float* demb, const float* emb_out, const int32_t* sort_ids, const int32_t* sort_perm,
+                        void* stream) {
+    return text_backward_impl(enc, buf, input_ids, nullptr, indices, cu_seqlens, Bc, S, T, max_seqlen, demb, emb_out, sort_ids,
+                              sort_perm, stream);
+}
+int cx_encoder_backward_typed(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                              const int64_t* token_type_ids, const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S,
+                              int T, int max_seqlen, const float* demb, const float* emb_out, const int32_t* sort_ids,
+                              const int32_t* sort_perm, void* stream) {
+    return text_backward_impl(enc, buf, input_ids, token_type_ids, indices, cu_seqlens, Bc, S, T, max_seqlen, demb, emb_out,
+                              sort_ids, sort_perm, stream);
 }
 
 // ---- token-level outputs (MLM head, sc/models/encoder/modeling_nomic_bert.py:590-669): same trunk, no pooling ------

@@ -397,8 +397,11 @@ __global__ __launch_bounds__(256, CS ? 3 : 4) void ln_bwd_pooled_kernel(const fl
     finish_param_grads<NCH, CS>(dg, db, dc, dgamma, dbeta, part, part3, smem);
 }
 
-template <int NCH>
+// TY: token_type_ids select row 0 or 1 of the (2, d) type table per token (wave-uniform); without it every token takes the
+// row type0 points at and the code is the untyped kernel's, instruction for instruction.
+template <int NCH, bool TY>
 __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __restrict__ ids,
+                                                           const int64_t* __restrict__ tts,
                                                            const int32_t* __restrict__ indices,
                                                            const float* __restrict__ word,
                                                            const float* __restrict__ type0,
@@ -409,17 +412,20 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
                                                            int T, int S, float eps) {
     constexpr int D = NCH * 256;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float g[NCH][4], b[NCH][4], ty[NCH][4];
+    float g[NCH][4], b[NCH][4], ty[NCH][4], ty1[TY ? NCH : 1][4];
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
         load4_f32(beta + (i * 64 + lane) * 4, b[i]);
         load4_f32(type0 + (i * 64 + lane) * 4, ty[i]);
+        if constexpr (TY) load4_f32(type0 + D + (i * 64 + lane) * 4, ty1[i]);
     }
     for (int t = blockIdx.x * 4 + wave; t < T; t += gridDim.x * 4) {
         const int flat = indices[t];
         const long id = ids[flat];
         const int pos = flat % S;
+        bool second = false;
+        if constexpr (TY) second = tts[flat] != 0;
         float z[NCH][4];
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -433,7 +439,10 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
                 for (int e = 0; e < 4; ++e) z[i][e] += pe[e];
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) z[i][e] += ty[i][e];
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (TY) z[i][e] += second ? ty1[i][e] : ty[i][e];
+                else z[i][e] += ty[i][e];
+            }
         }
         float mean, rstd;
         row_stats<NCH>(z, D, eps, mean, rstd);
@@ -451,27 +460,34 @@ __global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const int64_t* __rest
     }
 }
 
-template <int NCH>
+// TY: as in the forward; the gradients of both type rows accumulate in registers per wave and leave the block as plain
+// stores into type_part[blk][2][D], dgamma / dbeta into a second [gridDim.x][2][D] behind it; ln_param_reduce_kernel folds
+// both in block order (no atomics on the type rows, nor on dgamma / dbeta: the typed backward's parameter gradients are
+// the same bits on every run).
+template <int NCH, bool TY>
 __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
     const bf16_t* __restrict__ da, const bf16_t* __restrict__ dbb, const int64_t* __restrict__ ids,
-    const int32_t* __restrict__ indices, const float* __restrict__ word, const float* __restrict__ type0,
+    const int64_t* __restrict__ tts, float* __restrict__ type_part, const int32_t* __restrict__ indices, const float* __restrict__ word, const float* __restrict__ type0,
     const float* __restrict__ pos_emb, const float* __restrict__ gamma, const float* __restrict__ mean_i,
     const float* __restrict__ rstd_i, float* dword, float* dtype0, float* dpos, float* dgamma, float* dbeta, int T,
     int S, int padding_idx, float* __restrict__ dz_out) {
     constexpr int D = NCH * 256;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float g[NCH][4], ty[NCH][4], dg[NCH][4], db[NCH][4], dty[NCH][4];
+    float g[NCH][4], ty[NCH][4], dg[NCH][4], db[NCH][4], dty[NCH][4], ty1[TY ? NCH : 1][4], dty1[TY ? NCH : 1][4];
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
         load4_f32(gamma + (i * 64 + lane) * 4, g[i]);
         load4_f32(type0 + (i * 64 + lane) * 4, ty[i]);
+        if constexpr (TY) load4_f32(type0 + D + (i * 64 + lane) * 4, ty1[i]);
     }
-    zero_acc(dg), zero_acc(db), zero_acc(dty);
+    zero_acc(dg), zero_acc(db), zero_acc(dty), zero_acc(dty1);
     for (int t = blockIdx.x * 4 + wave; t < T; t += gridDim.x * 4) {
         const int flat = indices[t];
         const long id = ids[flat];
         const int pos = flat % S;
+        bool second = false;
+        if constexpr (TY) second = tts[flat] != 0;
         const float mean = mean_i[t], rstd = rstd_i[t];
         float dy[NCH][4], xh[NCH][4];
         float s1 = 0.f, s2 = 0.f;
@@ -494,7 +510,10 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
                 for (int e = 0; e < 4; ++e) zz[e] += pe[e];
             }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) zz[e] += ty[i][e];
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (TY) zz[e] += second ? ty1[i][e] : ty[i][e];
+                else zz[e] += ty[i][e];
+            }
 #pragma unroll
             for (int e = 0; e < 4; ++e)
                 xh[i][e] = ln_bwd_accum(zz[e], g[i][e], dy[i][e], mean, rstd, s1, s2, dg[i][e], db[i][e]);
@@ -509,7 +528,11 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
             for (int e = 0; e < 4; ++e) {
                 const float o = ln_bwd_dz(g[i][e], dy[i][e], xh[i][e], s1, s2, rstd);
                 ov[e] = o;
-                dty[i][e] += o;
+                if constexpr (TY) {
+                    if (second) dty1[i][e] += o; else dty[i][e] += o;
+                } else {
+                    dty[i][e] += o;
+                }
                 // nn.Embedding(padding_idx=...) gives that row no gradient (sc/layers/embedding.py:581)
                 if (!dz_out && dword && id != padding_idx) unsafeAtomicAdd(dword + (size_t)id * D + col + e, o);
                 if (dpos) unsafeAtomicAdd(dpos + (size_t)pos * D + col + e, o);
@@ -520,12 +543,18 @@ __global__ __launch_bounds__(256) void embed_ln_bwd_kernel(
             if (dz_out) *reinterpret_cast<float4*>(dz_out + (size_t)t * D + col) = make_float4(ov[0], ov[1], ov[2], ov[3]);
         }
     }
-    fold_param_grads<NCH>(dg, db, dgamma, dbeta, nullptr, smem);
-    __syncthreads();
-    // type-embedding row 0 receives the sum over every token: reuse the same block fold.
-    float zero[NCH][4];
-    zero_acc(zero);
-    fold_param_grads<NCH>(dty, zero, dtype0, nullptr, nullptr, smem);
+    if constexpr (TY) {
+        fold_param_grads<NCH>(dg, db, nullptr, nullptr, type_part + (size_t)gridDim.x * 2 * D, smem);
+        __syncthreads();
+        fold_param_grads<NCH>(dty, dty1, nullptr, nullptr, type_part, smem);
+    } else {
+        fold_param_grads<NCH>(dg, db, dgamma, dbeta, nullptr, smem);
+        __syncthreads();
+        // type-embedding row 0 receives the sum over every token: reuse the same block fold.
+        float zero[NCH][4];
+        zero_acc(zero);
+        fold_param_grads<NCH>(dty, zero, dtype0, nullptr, nullptr, smem);
+    }
 }
 
 // Word-embedding gradient without atomics (the scatter of 100 M fp32 atomics cost 1.4 ms per 131072-token chunk and made the
@@ -1013,9 +1042,23 @@ int cx_embed_ln_fwd(const int64_t* input_ids, const int32_t* indices, const floa
                     float* rstd, int T, int S, int d, float eps, void* stream) {
     if (T <= 0) return CX_OK;
     if (!input_ids || !indices || !word || !type0 || !gamma || !beta || !out) return CX_ERR_ARG;
-    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_fwd_kernel<NCH>), dim3(ln_grid(T)), dim3(256), 0,
-                                         (hipStream_t)stream, input_ids, indices, word, type0, pos_emb, gamma, beta,
-                                         out, mean, rstd, T, S, eps));
+    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_fwd_kernel<NCH, false>), dim3(ln_grid(T)), dim3(256), 0,
+                                         (hipStream_t)stream, input_ids, (const int64_t*)nullptr, indices, word, type0, pos_emb,
+                                         gamma, beta, out, mean, rstd, T, S, eps));
+    return done();
+}
+
+int cx_embed_ln_fwd_typed(const int64_t* input_ids, const int64_t* token_type_ids, const int32_t* indices, const float* word,
+                          const float* type, int type_vocab_size, const float* pos_emb, const float* gamma, const float* beta,
+                          uint16_t* out, float* mean, float* rstd, int T, int S, int d, float eps, void* stream) {
+    if (type_vocab_size != 2) return CX_ERR_SHAPE;
+    if (!token_type_ids)
+        return cx_embed_ln_fwd(input_ids, indices, word, type, pos_emb, gamma, beta, out, mean, rstd, T, S, d, eps, stream);
+    if (T <= 0) return CX_OK;
+    if (!input_ids || !indices || !word || !type || !gamma || !beta || !out) return CX_ERR_ARG;
+    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_fwd_kernel<NCH, true>), dim3(ln_grid(T)), dim3(256), 0,
+                                         (hipStream_t)stream, input_ids, token_type_ids, indices, word, type, pos_emb, gamma,
+                                         beta, out, mean, rstd, T, S, eps));
     return done();
 }
 
@@ -1026,11 +1069,50 @@ int cx_embed_ln_bwd(const uint16_t* dout_a, const uint16_t* dout_b, const int64_
     if (T <= 0) return CX_OK;
     if (!dout_a || !input_ids || !indices || !word || !type0 || !gamma || !mean || !rstd) return CX_ERR_ARG;
     const size_t smem = (size_t)8 * d * sizeof(float);
-    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_bwd_kernel<NCH>), dim3(ln_grid_bwd(T)), dim3(256), smem,
-                                         (hipStream_t)stream, dout_a, dout_b, input_ids, indices, word, type0,
-                                         pos_emb, gamma, mean, rstd, dword, dtype0, dpos, dgamma, dbeta, T, S,
-                                         padding_idx, (float*)nullptr));
+    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_bwd_kernel<NCH, false>), dim3(ln_grid_bwd(T)), dim3(256), smem,
+                                         (hipStream_t)stream, dout_a, dout_b, input_ids, (const int64_t*)nullptr,
+                                         (float*)nullptr, indices, word, type0, pos_emb, gamma, mean, rstd, dword, dtype0,
+                                         dpos, dgamma, dbeta, T, S, padding_idx, (float*)nullptr));
     return done();
+}
+
+namespace {
+// The typed backward's grid: the untyped launcher's, capped by the block partials the workspace holds -- per block [2][d] for
+// the type rows and [2][d] for dgamma / dbeta.  0: the workspace holds none.
+int typed_grid(int grid, const float* ws, long ws_floats, int d) {
+    if (!ws || ws_floats < 4L * d) return 0;
+    const long cap = ws_floats / (4L * d);
+    return grid > cap ? (int)cap : grid;
+}
+int typed_finish(float* ws, float* dtype, float* dgamma, float* dbeta, int grid, int d, void* stream) {
+    if (dtype)
+        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * d + 63) / 64), dim3(256), 0, (hipStream_t)stream, ws, dtype, dtype + d,
+                           grid, d);
+    if (dgamma || dbeta)
+        hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((2 * d + 63) / 64), dim3(256), 0, (hipStream_t)stream,
+                           ws + (size_t)grid * 2 * d, dgamma, dbeta, grid, d);
+    return done();
+}
+}  // namespace
+
+int cx_embed_ln_bwd_typed(const uint16_t* dout_a, const uint16_t* dout_b, const int64_t* input_ids,
+                          const int64_t* token_type_ids, const int32_t* indices, const float* word, const float* type,
+                          int type_vocab_size, const float* pos_emb, const float* gamma, const float* mean, const float* rstd,
+                          float* dword, float* dtype, float* dpos, float* dgamma, float* dbeta, float* ws, long ws_floats, int T,
+                          int S, int d, int padding_idx, void* stream) {
+    if (type_vocab_size != 2) return CX_ERR_SHAPE;
+    if (!token_type_ids)
+        return cx_embed_ln_bwd(dout_a, dout_b, input_ids, indices, word, type, pos_emb, gamma, mean, rstd, dword, dtype, dpos,
+                               dgamma, dbeta, T, S, d, padding_idx, stream);
+    if (T <= 0) return CX_OK;
+    if (!dout_a || !input_ids || !indices || !word || !type || !gamma || !mean || !rstd) return CX_ERR_ARG;
+    const int grid = typed_grid(ln_grid_bwd(T), ws, ws_floats, d);
+    if (grid <= 0) return CX_ERR_ARG;
+    const size_t smem = (size_t)8 * d * sizeof(float);
+    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_bwd_kernel<NCH, true>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
+                                         dout_a, dout_b, input_ids, token_type_ids, ws, indices, word, type, pos_emb, gamma,
+                                         mean, rstd, dword, dtype, dpos, dgamma, dbeta, T, S, padding_idx, (float*)nullptr));
+    return typed_finish(ws, dtype, dgamma, dbeta, grid, d, stream);
 }
 
 int cx_embed_ln_bwd_sorted(const uint16_t* dout_a, const uint16_t* dout_b, const int64_t* input_ids,
@@ -1045,15 +1127,45 @@ int cx_embed_ln_bwd_sorted(const uint16_t* dout_a, const uint16_t* dout_b, const
     // many blocks here: without the word-row atomics this kernel is a plain streaming LayerNorm backward
     int grid = (T + 3) / 4;
     if (grid > 1024) grid = 1024;
-    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_bwd_kernel<NCH>), dim3(grid), dim3(256), smem, (hipStream_t)stream, dout_a,
-                                         dout_b, input_ids, indices, word, type0, pos_emb, gamma, mean, rstd, dword, dtype0,
-                                         dpos, dgamma, dbeta, T, S, padding_idx, dz_scratch));
+    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_bwd_kernel<NCH, false>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
+                                         dout_a, dout_b, input_ids, (const int64_t*)nullptr, (float*)nullptr, indices, word,
+                                         type0, pos_emb, gamma, mean, rstd, dword, dtype0, dpos, dgamma, dbeta, T, S,
+                                         padding_idx, dz_scratch));
     if (dword) {
         int sg = vocab < 8192 ? vocab : 8192;
         CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_scatter_sorted_kernel<NCH>), dim3(sg), dim3(256), 0, (hipStream_t)stream,
                                              dz_scratch, sorted_ids, perm, dword, T, vocab, padding_idx));
     }
     return done();
+}
+
+int cx_embed_ln_bwd_sorted_typed(const uint16_t* dout_a, const uint16_t* dout_b, const int64_t* input_ids,
+                                 const int64_t* token_type_ids, const int32_t* indices, const float* word, const float* type,
+                                 int type_vocab_size, const float* pos_emb, const float* gamma, const float* mean,
+                                 const float* rstd, float* dword, float* dtype, float* dpos, float* dgamma, float* dbeta,
+                                 float* ws, long ws_floats, int T, int S, int d, int padding_idx, int vocab,
+                                 const int32_t* sorted_ids, const int32_t* perm, float* dz_scratch, void* stream) {
+    if (type_vocab_size != 2) return CX_ERR_SHAPE;
+    if (!token_type_ids)
+        return cx_embed_ln_bwd_sorted(dout_a, dout_b, input_ids, indices, word, type, pos_emb, gamma, mean, rstd, dword, dtype,
+                                      dpos, dgamma, dbeta, T, S, d, padding_idx, vocab, sorted_ids, perm, dz_scratch, stream);
+    if (T <= 0) return CX_OK;
+    if (!dout_a || !input_ids || !indices || !word || !type || !gamma || !mean || !rstd) return CX_ERR_ARG;
+    if (!sorted_ids || !perm || !dz_scratch || vocab <= 0) return CX_ERR_ARG;
+    int grid = (T + 3) / 4;
+    if (grid > 1024) grid = 1024;
+    grid = typed_grid(grid, ws, ws_floats, d);
+    if (grid <= 0) return CX_ERR_ARG;
+    const size_t smem = (size_t)8 * d * sizeof(float);
+    CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_ln_bwd_kernel<NCH, true>), dim3(grid), dim3(256), smem, (hipStream_t)stream,
+                                         dout_a, dout_b, input_ids, token_type_ids, ws, indices, word, type, pos_emb, gamma,
+                                         mean, rstd, dword, dtype, dpos, dgamma, dbeta, T, S, padding_idx, dz_scratch));
+    if (dword) {
+        int sg = vocab < 8192 ? vocab : 8192;
+        CX_LN_DISPATCH(d, hipLaunchKernelGGL((embed_scatter_sorted_kernel<NCH>), dim3(sg), dim3(256), 0, (hipStream_t)stream,
+                                             dz_scratch, sorted_ids, perm, dword, T, vocab, padding_idx));
+    }
+    return typed_finish(ws, dtype, dgamma, dbeta, grid, d, stream);
 }
 
 }  // extern "C"

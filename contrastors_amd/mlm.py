@@ -135,6 +135,22 @@ class NomicBertForPreTraining(torch.nn.Module):
         sd["cls.predictions.decoder.weight"] = sd["bert." + _WORD]  # tied (:613-615)
         return sd
 
+    def save_pretrained(self, output_dir: str):
+        """model.safetensors with the reference's keys + config.json carrying the trunk architecture: the directory a
+        fine-tuning recipe names as `model_args.checkpoint` (contrastors_amd.seqcls takes `bert.*` and skips `cls.*`)."""
+        import dataclasses
+        import json
+        import os
+
+        from safetensors.torch import save_file
+
+        os.makedirs(output_dir, exist_ok=True)
+        save_file({k: v.detach().cpu().contiguous().clone() for k, v in self.reference_state_dict().items()},
+                  os.path.join(output_dir, "model.safetensors"))
+        with open(os.path.join(output_dir, "config.json"), "w") as f:
+            json.dump({"architectures": ["NomicBertForPreTraining"], "trunk_config": dataclasses.asdict(self.config),
+                       "trunk_type": "NomicBertConfig"}, f, indent=1)
+
     @torch.no_grad()
     def load_reference_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         self.bert.load_reference_state_dict({k[5:]: v for k, v in sd.items() if k.startswith("bert.")}, strict=strict)

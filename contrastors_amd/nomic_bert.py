@@ -254,6 +254,17 @@ class VarlenBatch:
     T: int
     max_seqlen: int
     _sort: Optional[tuple] = None  # (sorted ids int32, permutation int32): built on first use by a backward
+    token_type_ids: Optional[torch.Tensor] = None  # (B,S) int64 segment ids 0 / 1 (sentence pairs), None: every token type 0
+
+    def with_token_types(self, token_type_ids: Optional[torch.Tensor]) -> "VarlenBatch":
+        """Attach segment ids: they are indexed like input_ids, so they must match it in shape, dtype and device."""
+        if token_type_ids is not None:
+            if token_type_ids.shape != self.input_ids.shape or token_type_ids.dtype != torch.int64 \
+                    or token_type_ids.device != self.input_ids.device:
+                raise ValueError("token_type_ids must be an int64 tensor of input_ids' shape on its device")
+            token_type_ids = token_type_ids.contiguous()
+        self.token_type_ids = token_type_ids
+        return self
 
     def embedding_sort(self):
         """Token ids of the chunk in ascending stable order + the permutation that sorts them: lets the engine reduce the
@@ -903,16 +914,28 @@ class NomicBertEngine(torch.nn.Module):
         arena = self._get_arena(vb.T, vb.B, save_for_backward)
         self._arm_dropout(arena)
         self._desc.normalize = int(self.normalize_default if normalize is None else normalize)
-        rc = self.lib.cx_encoder_forward(C.byref(self._desc), C.byref(arena.desc), vb.input_ids.data_ptr(),
-                                         vb.indices.data_ptr(), vb.cu_seqlens.data_ptr(), vb.B, vb.S, vb.T,
-                                         vb.max_seqlen, int(save_for_backward), out.data_ptr(), _C.cur_stream())
-        _C.check(rc, "cx_encoder_forward")
+        if vb.token_type_ids is None:
+            rc = self.lib.cx_encoder_forward(C.byref(self._desc), C.byref(arena.desc), vb.input_ids.data_ptr(),
+                                             vb.indices.data_ptr(), vb.cu_seqlens.data_ptr(), vb.B, vb.S, vb.T,
+                                             vb.max_seqlen, int(save_for_backward), out.data_ptr(), _C.cur_stream())
+            _C.check(rc, "cx_encoder_forward")
+        else:
+            self._check_token_types()
+            rc = self.lib.cx_encoder_forward_typed(C.byref(self._desc), C.byref(arena.desc), vb.input_ids.data_ptr(),
+                                                   vb.token_type_ids.data_ptr(), vb.indices.data_ptr(),
+                                                   vb.cu_seqlens.data_ptr(), vb.B, vb.S, vb.T, vb.max_seqlen,
+                                                   int(save_for_backward), out.data_ptr(), _C.cur_stream())
+            _C.check(rc, "cx_encoder_forward_typed")
         if save_for_backward:
             arena.emb_out = out
             arena.normalize = self._desc.normalize
             self._outstanding += 1
             return out, arena
         return out, None
+
+    def _check_token_types(self):
+        if self.config.type_vocab_size != 2:
+            raise NotImplementedError(f"token_type_ids need type_vocab_size == 2 (the config has {self.config.type_vocab_size})")
 
     def drop_idle_arenas(self):
         """Give every pooled (idle) activation arena back to the allocator: a schedule change (another batch shape, another
@@ -930,11 +953,19 @@ class NomicBertEngine(torch.nn.Module):
         self._desc.normalize = arena.normalize
         sids, perm = vb.embedding_sort()
         fires = self._begin_backward(arena)
-        rc = self.lib.cx_encoder_backward(C.byref(self._desc), C.byref(arena.desc), vb.input_ids.data_ptr(),
-                                          vb.indices.data_ptr(), vb.cu_seqlens.data_ptr(), vb.B, vb.S, vb.T,
-                                          vb.max_seqlen, demb.data_ptr(), arena.emb_out.data_ptr(), _C.ptr(sids),
-                                          _C.ptr(perm), _C.cur_stream())
-        _C.check(rc, "cx_encoder_backward")
+        if vb.token_type_ids is None:
+            rc = self.lib.cx_encoder_backward(C.byref(self._desc), C.byref(arena.desc), vb.input_ids.data_ptr(),
+                                              vb.indices.data_ptr(), vb.cu_seqlens.data_ptr(), vb.B, vb.S, vb.T,
+                                              vb.max_seqlen, demb.data_ptr(), arena.emb_out.data_ptr(), _C.ptr(sids),
+                                              _C.ptr(perm), _C.cur_stream())
+            _C.check(rc, "cx_encoder_backward")
+        else:
+            rc = self.lib.cx_encoder_backward_typed(C.byref(self._desc), C.byref(arena.desc), vb.input_ids.data_ptr(),
+                                                    vb.token_type_ids.data_ptr(), vb.indices.data_ptr(),
+                                                    vb.cu_seqlens.data_ptr(), vb.B, vb.S, vb.T, vb.max_seqlen,
+                                                    demb.data_ptr(), arena.emb_out.data_ptr(), _C.ptr(sids), _C.ptr(perm),
+                                                    _C.cur_stream())
+            _C.check(rc, "cx_encoder_backward_typed")
         self._end_backward(arena, fires)
 
     def _begin_backward(self, arena: _ChunkArena) -> bool:
@@ -988,8 +1019,8 @@ class NomicBertEngine(torch.nn.Module):
 
     # nn.Module-style call used by BiEncoder: differentiable w.r.t. the engine's own parameters
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                normalize: Optional[bool] = None) -> torch.Tensor:
-        vb = VarlenBatch.from_mask(input_ids, attention_mask)
+                normalize: Optional[bool] = None, token_type_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        vb = VarlenBatch.from_mask(input_ids, attention_mask).with_token_types(token_type_ids)
         if torch.is_grad_enabled() and self.training:
             return _EncodeFn.apply(self.flat_decay, self, vb, normalize)
         emb, _ = self.forward_chunk(vb, False, normalize)

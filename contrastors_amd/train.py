@@ -4,7 +4,8 @@ torchrun / `python -m torch.distributed.run` launches one process per GPU; backe
 named like fields of train_args / model_args / data_args override the YAML (sc/train.py:87-94).  Data: with
 `data_args.input_shards` pointing at a spec YAML of LOCAL shards (contrastors_amd/data.py; S3 transport is not built) and
 `--synthetic-steps 0` the streaming loader feeds the trainer (the tokenizer named by `model_args.tokenizer_name` must be
-available offline); otherwise `--synthetic-steps N` drives it with synthetic batches of the loader's exact key contract.
+available offline); otherwise `--synthetic-steps N` drives it with synthetic batches of the loader's exact key contract.  `model_type: glue` reads
+`--input_shards DIR --task_name rte` (a local directory with the task's splits) and runs its own epoch loop.
 """
 from __future__ import annotations
 
@@ -99,9 +100,17 @@ def main():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     config = apply_overrides(read_config(args.config), overrides)
-    if config.model_args.model_type not in TRAINER_REGISTRY:   # glue / mmlm: valid reference types, not on this path
+    if config.model_args.model_type not in TRAINER_REGISTRY:   # mmlm: a valid reference type, not on this path
         raise NotImplementedError(f"model_type {config.model_args.model_type!r}: this build serves {sorted(TRAINER_REGISTRY)} "
-                                  "(the contrastive, image-text, MLM and distillation trainers)")
+                                  "(the contrastive, image-text, MLM, distillation and GLUE trainers)")
+    if config.model_args.model_type == "glue":
+        # sc/trainers/glue.py: the trainer owns its data (data_args.input_shards = a local directory with the task's splits,
+        # data_args.task_name) and its epoch loop: num_epochs passes, the GLUE metric after each
+        trainer = TRAINER_REGISTRY["glue"](config, torch.bfloat16)
+        trainer.train(log_every=10)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     trainer = TRAINER_REGISTRY[config.model_args.model_type](config, torch.bfloat16, total_steps=args.synthetic_steps)
     per_rank = config.data_args.batch_size // world
     if args.synthetic_steps <= 0 and config.data_args.input_shards:

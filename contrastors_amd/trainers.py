@@ -611,7 +611,7 @@ class ImageTextTrainer(TextTextTrainer):
         return out["loss"].detach()
 
 
-# sc/trainers/__init__.py:9-17 (the contrastive entries, MLM pretraining and distillation; the glue trainer is outside the hot path)
+# sc/trainers/__init__.py:9-17 (the contrastive entries, MLM pretraining, distillation and GLUE fine-tuning)
 def _mlm_trainer(*a, **k):
     from .mlm import MLMTrainer  # imported lazily: mlm.py imports this module's schedule helper
 
@@ -624,8 +624,14 @@ def _distill_trainer(*a, **k):
     return DistillTrainer(*a, **k)
 
 
+def _glue_trainer(*a, **k):
+    from .glue import GlueTrainer  # imported lazily: glue.py imports this module's schedule helper
+
+    return GlueTrainer(*a, **k)
+
+
 TRAINER_REGISTRY = {"encoder": TextTextTrainer, "image_text": ImageTextTrainer, "locked_text": ImageTextTrainer,
-                    "mlm": _mlm_trainer, "distill": _distill_trainer}
+                    "mlm": _mlm_trainer, "distill": _distill_trainer, "glue": _glue_trainer}
 
 
 def synthetic_batches(n_steps: int, per_rank_batch: int, seq_len: int, vocab: int = 30522, seed: int = 1234,

@@ -175,6 +175,31 @@ int cx_embed_ln_bwd_sorted(const uint16_t* dout_a, const uint16_t* dout_b, const
                            float* dpos, float* dgamma, float* dbeta, int T, int S, int d, int padding_idx, int vocab,
                            const int32_t* sorted_ids, const int32_t* perm, float* dz_scratch, void* stream);
 
+/* The three entry points above with token-type (segment) ids (sc/layers/embedding.py:607-614; sentence-pair tasks): token t
+ * takes row token_type_ids[flat] of `type`:(type_vocab_size, d) -- token_type_ids:(B*S) int64 is indexed with indices[t] exactly
+ * like input_ids -- and `dtype`:(type_vocab_size, d) receives both rows' gradients.  type_vocab_size must be 2 (anything else:
+ * CX_ERR_SHAPE, nothing launched); an id other than 0 selects row 1.  token_type_ids == NULL calls the untyped entry point with
+ * row 0: the same bits, for the output and every gradient.  The backward forms accumulate the type rows in registers per wave
+ * and fold the block partials -- of the type rows and of dgamma / dbeta -- through ws (fp32, >= 4 * d floats: [blocks][2][d]
+ * twice; the grid is capped by what it holds; CX_ERR_ARG if it holds none) with the LayerNorm backward's second-stage
+ * reduction: no atomics on the type rows, dgamma or dbeta, which are the same bits on every run (dpos, and dword in the
+ * unsorted form, remain fp32 atomics).
+ * Additive: cx_abi_version stays 10. */
+int cx_embed_ln_fwd_typed(const int64_t* input_ids, const int64_t* token_type_ids, const int32_t* indices, const float* word,
+                          const float* type, int type_vocab_size, const float* pos_emb, const float* gamma, const float* beta,
+                          uint16_t* out, float* mean, float* rstd, int T, int S, int d, float eps, void* stream);
+int cx_embed_ln_bwd_typed(const uint16_t* dout_a, const uint16_t* dout_b, const int64_t* input_ids,
+                          const int64_t* token_type_ids, const int32_t* indices, const float* word, const float* type,
+                          int type_vocab_size, const float* pos_emb, const float* gamma, const float* mean, const float* rstd,
+                          float* dword, float* dtype, float* dpos, float* dgamma, float* dbeta, float* ws, long ws_floats, int T,
+                          int S, int d, int padding_idx, void* stream);
+int cx_embed_ln_bwd_sorted_typed(const uint16_t* dout_a, const uint16_t* dout_b, const int64_t* input_ids,
+                                 const int64_t* token_type_ids, const int32_t* indices, const float* word, const float* type,
+                                 int type_vocab_size, const float* pos_emb, const float* gamma, const float* mean,
+                                 const float* rstd, float* dword, float* dtype, float* dpos, float* dgamma, float* dbeta,
+                                 float* ws, long ws_floats, int T, int S, int d, int padding_idx, int vocab,
+                                 const int32_t* sorted_ids, const int32_t* perm, float* dz_scratch, void* stream);
+
 /* ---- K10 swiglu (flash_attn.ops.activations.swiglu; sc/layers/mlp.py:75) and GELU(erf) (mlp.py:30-34) ----
  * yg:(T, 2*I) holds y = fc11(x) and gate = fc12(x);  act = silu(gate) * y, fp32 math, one rounding.
  * layout 0: yg = [y | gate] concatenated; layout 1: interleaved in groups of 32 columns
@@ -397,6 +422,28 @@ int cx_simkl_bwd(const float* Qs, const float* Ds, const float* Qt, const float*
                  const float* lse_t, float inv_temp, float coef, float* Gmat, float* GmatT, float* QsT, float* DsT,
                  float* dQs, float* dDs, int N, int G, int dim_s, int dim_t, int ldqs, int ldds, int ldqt, int lddt,
                  void* stream);
+/* ---- the sequence-classification head (sc/models/encoder/modeling_nomic_bert.py:398-414 NomicBertPooler, 672-757
+ * NomicBertForSequenceClassification): pooled = tanh(X Wp^T + bp); h = dropout(pooled, p); logits = h Wc^T + bc; then
+ *   mode 0  cross-entropy: labels:(B) int64, loss_rows[b] = lse(logits[b]) - logits[b][label]; a label outside [0, C) (-100, the
+ *           ignore index, among them) gives the row loss 0 and no gradient;
+ *   mode 1  MSE: labels:(B, C) fp32, loss_rows[b] = mean_c (logits[b][c] - labels[b][c])^2.
+ * The host takes the mean (over the counted rows).  X:(B, d) fp32 with row stride ldx >= d, ldx % 4 == 0 (the engine's cls-pooled,
+ * un-normalised output); Wp:(d, d), bp:(d), Wc:(C, d), bc:(C) fp32.  Outputs pooled:(B, d), logits:(B, C), loss_rows:(B) fp32;
+ * labels == NULL: logits only.  The dropout mask is dropout_keep4 of (seed, offset) over element b * d + j and is regenerated by
+ * the backward, never stored; p = 0 is no dropout.  fp32 accumulation, no atomics, every sum in one fixed order: a repeated call
+ * gives the same bits.  d in {256, 512, 768, 1024}, 1 <= C <= 8, 1 <= B <= 4096 (CX_ERR_SHAPE); a NULL required pointer, a mode
+ * other than 0 / 1 or p outside [0, 1): CX_ERR_ARG; neither launches anything.  Two launches forward, two backward.
+ * Additive: cx_abi_version stays 10. */
+long cx_seqcls_ws_floats(int B, int d, int C);
+int cx_seqcls_head_fwd(const float* X, long ldx, const float* Wp, const float* bp, const float* Wc, const float* bc,
+                       const void* labels, int mode, float p, unsigned long long seed, unsigned long long offset, float* pooled,
+                       float* logits, float* loss_rows, int B, int d, int C, void* stream);
+/* backward of  coef * sum_b loss_rows[b]:  dWp:(d, d), dbp:(d), dWc:(C, d), dbc:(C), dX:(B, d) fp32 are OVERWRITTEN (dX is the demb
+ * of cx_encoder_backward_typed).  pooled / logits: what the forward wrote; ws: cx_seqcls_ws_floats(B, d, C) floats. */
+int cx_seqcls_head_bwd(const float* X, long ldx, const float* Wp, const float* Wc, const float* pooled, const float* logits,
+                       const void* labels, int mode, float coef, float p, unsigned long long seed, unsigned long long offset,
+                       float* ws, long ws_floats, float* dWp, float* dbp, float* dWc, float* dbc, float* dX, int B, int d, int C,
+                       void* stream);
 /* ---- the same loss on the fp8 matrix-core path (BASELINE.json configs[4] "fp8 MFMA similarity GEMM"; the reference
  * only carries the `use_fp8` flag, configs/train/contrastive_pretrain.yaml:24).  Rows are quantised to OCP e4m3 with
  * one scale per row, the contraction is v_mfma_scale_f32_32x32x64_f8f6f4 (fp32 accumulate, online fp32 log-sum-exp);
@@ -563,6 +610,16 @@ int cx_encoder_backward(const CxEncoderDesc* enc, const CxChunkBuffers* buf, con
 /* sort_ids / sort_perm (both int32[T], or both NULL): the chunk's token ids in ascending stable order and the permutation
  * that sorts them -- with them the word-embedding gradient is a deterministic segmented reduction
  * (cx_embed_ln_bwd_sorted), without them fp32 atomics. */
+
+/* The pooled pair with token-type ids (sentence-pair tasks): token_type_ids:(Bc,S) int64 segment ids 0 / 1, NULL = the pair
+ * above, bit for bit.  enc->type_emb / gtype_emb are the (2, d) table and its gradient.  Routed to cx_embed_ln_*_typed. */
+int cx_encoder_forward_typed(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                             const int64_t* token_type_ids, const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S,
+                             int T, int max_seqlen, int save_for_backward, float* emb_out, void* stream);
+int cx_encoder_backward_typed(const CxEncoderDesc* enc, const CxChunkBuffers* buf, const int64_t* input_ids,
+                              const int64_t* token_type_ids, const int32_t* indices, const int32_t* cu_seqlens, int Bc, int S,
+                              int T, int max_seqlen, const float* demb, const float* emb_out, const int32_t* sort_ids,
+                              const int32_t* sort_perm, void* stream);
 
 /* Token-level variant for heads that read every position (the MLM head of NomicBertForPreTraining,
  * sc/models/encoder/modeling_nomic_bert.py:590-669): hidden_out / dhidden are (T, d) bf16 in unpadded token order
