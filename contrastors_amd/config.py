@@ -7,7 +7,7 @@ are kept: Matryoshka + GradCache is rejected (config.py:70-77) and eval_strategy
 """
 from __future__ import annotations
 
-from typing import List, Optional, Union
+from typing import Any, Dict, List, Optional, Tuple, Union
 
 import yaml
 from pydantic import BaseModel, ConfigDict, model_validator
@@ -106,6 +106,25 @@ class DataArgs(BaseModel):
     document_max_length: Optional[int] = None
     mlm_prob: Optional[float] = None
     task_name: Optional[str] = None   # model_type: glue (sc/trainers/glue.py:50): cola, mnli, mrpc, qnli, qqp, rte, sst2, stsb
+    # model_type: image_text / locked_text (sc/config.py:123-136 ImageTextDataArgs; contrastors_amd/image_data.py).  All inert
+    # unless image_text_shards is set; imagenet_val_path / eval_flickr parse and are not used (no zero-shot / Flickr evaluation)
+    image_text_shards: Optional[str] = None
+    eval_batch_size: Optional[int] = None
+    imagenet_val_path: Optional[str] = None
+    eval_flickr: Optional[bool] = False
+    train_num_samples: Optional[int] = None
+    dataset_resampled: Optional[bool] = False
+
+
+class TransformsConfig(BaseModel):
+    """sc/config.py:215-221: the recipe's `transforms:` block (contrastors_amd/image_transform.py serves it)."""
+    model_config = ConfigDict(extra="ignore")
+    image_size: Union[int, Tuple[int, int]] = 224
+    mean: Optional[Union[float, Tuple[float, float, float]]] = (0.48145466, 0.4578275, 0.40821073)
+    std: Optional[Union[float, Tuple[float, float, float]]] = (0.26862954, 0.26130258, 0.27577711)
+    resize_longest_max: bool = False
+    fill_color: int = 0
+    aug_cfg: Optional[Dict[str, Any]] = None
 
 
 class ModelArgs(BaseModel):
@@ -177,6 +196,7 @@ class Config(BaseModel):
     text_model_args: Optional[ModelArgs] = None
     vision_model_args: Optional[ModelArgs] = None
     tower_model_args: Optional[ModelArgs] = None
+    transforms: Optional[TransformsConfig] = None   # sc/config.py:236 (image-text recipes)
     deepspeed: Optional[bool] = False
     deepspeed_config: Optional[dict] = None
 

@@ -6,6 +6,8 @@ named like fields of train_args / model_args / data_args override the YAML (sc/t
 `--synthetic-steps 0` the streaming loader feeds the trainer (the tokenizer named by `model_args.tokenizer_name` must be
 available offline); otherwise `--synthetic-steps N` drives it with synthetic batches of the loader's exact key contract.  `model_type: glue` reads
 `--input_shards DIR --task_name rte` (a local directory with the task's splits) and runs its own epoch loop.
+`model_type: image_text` / `locked_text` with `data_args.image_text_shards` (local tar shards of image / caption pairs) and
+`--synthetic-steps 0` trains from contrastors_amd/image_data.py for `data_args.train_num_samples // batch_size` steps.
 """
 from __future__ import annotations
 
@@ -111,9 +113,28 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    image_shards = (config.model_args.model_type in ("image_text", "locked_text") and args.synthetic_steps <= 0
+                    and config.data_args.image_text_shards)
+    if image_shards and not config.data_args.train_num_samples:
+        # sc/dataset/image_text_loader.py:398-410 falls back to the sizes of three named datasets; a local shard list has none
+        raise SystemExit("data_args.image_text_shards needs data_args.train_num_samples (the LR horizon: a tar stream has no length)")
     trainer = TRAINER_REGISTRY[config.model_args.model_type](config, torch.bfloat16, total_steps=args.synthetic_steps)
     per_rank = config.data_args.batch_size // world
-    if args.synthetic_steps <= 0 and config.data_args.input_shards:
+    if image_shards:
+        # sc/trainers/image_text.py:70-90: tar shards of image / caption pairs; the workers decode, the trainer's GpuImageTransform
+        # crops, resizes and normalizes on the GPU (contrastors_amd/image_data.py, image_transform.py)
+        from .image_data import get_image_text_loader
+
+        tok = None
+        if not config.text_model_args.precomputed:
+            from transformers import AutoTokenizer
+
+            tok = AutoTokenizer.from_pretrained(config.text_model_args.tokenizer_name, local_files_only=True)
+        loader = get_image_text_loader(config, tok, is_train=True, infinite=True)
+        steps = config.data_args.train_num_samples // config.data_args.batch_size
+        trainer.set_total_steps(steps)
+        trainer.train(iter(loader), max_steps=steps, log_every=10)
+    elif args.synthetic_steps <= 0 and config.data_args.input_shards:
         from transformers import AutoTokenizer
 
         from .data import get_streaming_dataset

@@ -518,6 +518,10 @@ class ImageTextTrainer(TextTextTrainer):
                  vision_trunk_config=None, total_steps: Optional[int] = None):
         self._trunks = (text_trunk_config, vision_trunk_config)
         super().__init__(config, dtype=dtype, device=device, total_steps=total_steps)
+        from .image_transform import GpuImageTransform   # sc/trainers/image_text.py:29-35 (the train transform; crops differ per rank)
+
+        self.image_transform = GpuImageTransform.from_config(config.transforms, is_train=True, out_dtype=torch.bfloat16,
+                                                             seed=config.data_args.seed + self.rank, device=self.device)
 
     # sc/trainers/image_text.py:53-68 + sc/models/dual_encoder/modeling_dual_encoder.py:10-24
     def get_model(self, config: Config, trunk_config=None) -> Dict[str, torch.nn.Module]:
@@ -568,7 +572,10 @@ class ImageTextTrainer(TextTextTrainer):
         if self.config.train_args.grad_cache:
             raise NotImplementedError("Grad cache not supported for three towers")  # the reference's own refusal
         text = {k: (v.to(self.device, non_blocking=True) if torch.is_tensor(v) else v) for k, v in batch["text"].items()}
-        vision = {k: v.to(self.device, non_blocking=True) for k, v in batch["vision"].items()}
+        if "pixels_u8" in batch["vision"]:   # a ragged batch of decoded images (image_data.py): crop, resize, normalize on the GPU
+            vision = {"input_ids": self.image_transform(batch["vision"])}
+        else:
+            vision = {k: v.to(self.device, non_blocking=True) for k, v in batch["vision"].items()}
         return self.model["model"](text, vision)
 
     def backward(self, loss):

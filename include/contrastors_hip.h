@@ -444,6 +444,26 @@ int cx_seqcls_head_bwd(const float* X, long ldx, const float* Wp, const float* W
                        const void* labels, int mode, float coef, float p, unsigned long long seed, unsigned long long offset,
                        float* ws, long ws_floats, float* dWp, float* dbp, float* dWc, float* dbc, float* dX, int B, int d, int C,
                        void* stream);
+/* ---- image crop + resize + normalize of the image-text data path (sc/dataset/transform.py: RandomResizedCrop(S, BICUBIC) or
+ * Resize(S, BICUBIC) + CenterCrop(S), then ToTensor + Normalize, which the reference runs with torchvision on PIL images).
+ * pixels: one ragged device buffer of HWC uint8 RGB images; image b starts at byte offsets[b] (any alignment) and is
+ * sizes[2b] rows x sizes[2b+1] columns.  plan_i[4b..] = (y_lo, y_hi, x_lo, x_hi): the clamp range [lo, hi) of the taps per axis;
+ * plan_f[4b..] = (y_origin, y_scale, x_origin, x_scale), float64: output pixel o of an axis is centred at
+ * origin + (o + 0.5) * scale source pixels.  The arithmetic is PIL's BICUBIC (a = -0.5, support 2 * max(scale, 1), weights
+ * normalised per output pixel): the horizontal pass is rounded half up and clamped to 0..255, the vertical pass runs on those
+ * 8-bit values and is rounded and clamped again, then out[b][c][y][x] = (level / 255 - mean[c]) / std[c], (B, 3, S, S) fp32
+ * (out_bf16 = 0) or bf16 (out_bf16 = 1).  One launch for the whole batch, the 8-bit intermediate stays in LDS; no atomics, a
+ * repeated call gives the same bits.  offsets (B + 1 entries, the last = the end of image B - 1), sizes, plan_i and plan_f are
+ * PINNED HOST memory (hipHostMalloc / torch pin_memory): the call reads them on the host -- the served-range check and the
+ * launch plan come from them -- and the kernel reads the same bytes through their device mapping, so they must stay unchanged
+ * until the launch has completed; pageable or device memory there is CX_ERR_ARG.  mean3 / std3: three host floats each.
+ * Served: 1 <= S <= 512, source sides 1..8192, 0 <= lo < hi <= side, scale in (0, 16] per axis (an upsample has no lower limit:
+ * its support stays at 2 source pixels), the first and last centre within one `scale` of [lo, hi], and offsets[b + 1] -
+ * offsets[b] >= 3 * h * w; anything else is CX_ERR_SHAPE.  A NULL pointer or B <= 0: CX_ERR_ARG.  Neither launches anything.
+ * Additive: cx_abi_version stays 10. */
+int cx_image_transform(const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, const int32_t* plan_i,
+                       const double* plan_f, void* out, int out_bf16, int B, int S, const float* mean3, const float* std3,
+                       void* stream);
 /* ---- the same loss on the fp8 matrix-core path (BASELINE.json configs[4] "fp8 MFMA similarity GEMM"; the reference
  * only carries the `use_fp8` flag, configs/train/contrastive_pretrain.yaml:24).  Rows are quantised to OCP e4m3 with
  * one scale per row, the contraction is v_mfma_scale_f32_32x32x64_f8f6f4 (fp32 accumulate, online fp32 log-sum-exp);
