@@ -196,6 +196,7 @@ _SIGS = {
     "cx_seqcls_head_bwd": (i32, [vp, i64, vp, vp, vp, vp, vp, i32, f32, f32, u64, u64, vp, i64, vp, vp, vp, vp, vp, i32, i32,
                                  i32, vp]),
     "cx_image_transform": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), C.POINTER(f32), vp]),
+    "cx_mlm_mask": (i32, [vp, i32, i64, vp, vp, vp, i32, i64, i32, f32, u64, u64, vp, vp, i32, i32, vp]),
     "cx_simkl_ws_floats": (i64, [i32, i32]),
     "cx_simkl_fwd": (i32, [vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cx_simkl_bwd": (i32, [vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

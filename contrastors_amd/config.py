@@ -105,6 +105,13 @@ class DataArgs(BaseModel):
     query_max_length: Optional[int] = None
     document_max_length: Optional[int] = None
     mlm_prob: Optional[float] = None
+    # model_type: mlm (sc/config.py MLMDataArgs; sc/trainers/mlm.py:54-99; contrastors_amd/mlm_data.py).  tokenized_dataset is a
+    # LOCAL path here (a datasets save_to_disk directory or an (N, S) .npy); mask_on is this path's key: device = cx_mlm_mask
+    # draws the masks on the GPU, host = the reference's collator on the loader workers
+    tokenized_dataset: Optional[str] = None
+    val_pct: Optional[float] = None
+    val_mlm_prob: Optional[float] = None
+    mask_on: str = "device"
     task_name: Optional[str] = None   # model_type: glue (sc/trainers/glue.py:50): cola, mnli, mrpc, qnli, qqp, rte, sst2, stsb
     # model_type: image_text / locked_text (sc/config.py:123-136 ImageTextDataArgs; contrastors_amd/image_data.py).  All inert
     # unless image_text_shards is set; imagenet_val_path / eval_flickr parse and are not used (no zero-shot / Flickr evaluation)
@@ -114,6 +121,16 @@ class DataArgs(BaseModel):
     eval_flickr: Optional[bool] = False
     train_num_samples: Optional[int] = None
     dataset_resampled: Optional[bool] = False
+
+    @model_validator(mode="after")
+    def _mlm_keys(self):
+        if self.mask_on not in ("device", "host"):
+            raise ValueError(f"data_args.mask_on must be device or host, got {self.mask_on!r}")
+        if self.val_pct is not None and not 0.0 <= self.val_pct < 1.0:
+            raise ValueError(f"data_args.val_pct must be in [0, 1), got {self.val_pct}")
+        if self.val_mlm_prob is not None and not 0.0 <= self.val_mlm_prob < 1.0:
+            raise ValueError(f"data_args.val_mlm_prob must be in [0, 1), got {self.val_mlm_prob}")
+        return self
 
 
 class TransformsConfig(BaseModel):

@@ -287,6 +287,182 @@ class MLMTrainer:
         finally:
             model.train(was)
 
+    # ---- the data path of the recipe: loaders of contrastors_amd/mlm_data.py, evaluation, checkpoints, the epoch loop -----------
+    ordinal = 0          # micro-batches masked since the start of the run: the Philox offset of the next training batch
+    epoch = 0            # where the run stands: a resume starts at batch `batch_in_epoch` of `epoch`
+    batch_in_epoch = 0
+    tracker = None
+    masker = None
+    eval_masker = None
+
+    @property
+    def rank(self) -> int:
+        return dist.get_rank() if self.distributed else 0
+
+    def set_total_steps(self, total_steps: int):
+        """The LR horizon in micro-batches, from the loader's length (sc/trainers/mlm.py:97), before the first step."""
+        from .trainers import _lr_lambda
+
+        if self.step != 0:
+            raise RuntimeError("set_total_steps after training started")
+        ta = self.config.train_args
+        self.total_steps = max(1, int(total_steps))
+        warm = ta.warmup_steps if ta.warmup_steps is not None else int(ta.warmup_pct * self.total_steps)
+        self.scheduler = torch.optim.lr_scheduler.LambdaLR(self.optimizer, _lr_lambda(ta.schedule_type, warm, self.total_steps))
+
+    def attach_maskers(self, info):
+        """Training masks under (data_args.seed, mlm_prob), evaluation masks under (seed + 1, val_mlm_prob); none under mask_on: host."""
+        from .mlm_data import GpuMlmMasker
+
+        da = self.config.data_args
+        if da.mask_on == "host":   # the collator draws the masks: the batches arrive with labels
+            return
+        p = da.mlm_prob if da.mlm_prob is not None else 0.3
+        self.masker = GpuMlmMasker(info, p, da.seed, device=self.device)
+        self.eval_masker = GpuMlmMasker(info, da.val_mlm_prob if da.val_mlm_prob is not None else p, da.seed + 1, device=self.device)
+
+    def _masked(self, batch, masker, ordinal):
+        if "labels" in batch:   # mask_on: host -- the collator has drawn the masks
+            return batch
+        if masker is None:
+            raise RuntimeError("a batch without labels needs the device masker: call attach_maskers(info), or give fit() the loaders of get_mlm_loaders")
+        return masker(batch, ordinal, self.rank, self.world)
+
+    def log(self, metrics, step=None):   # sc/trainers/base.py:137-139
+        if self.rank == 0 and self.tracker is not None:
+            self.tracker.log(metrics, step=step)
+
+    def _mean_over_ranks(self, loss: torch.Tensor) -> torch.Tensor:
+        loss = loss.detach().float()
+        if self.world > 1:
+            loss = loss.clone()
+            dist.all_reduce(loss)
+            loss /= self.world
+        return loss
+
+    @torch.no_grad()
+    def eval_loop(self, loader, step):
+        """sc/trainers/mlm.py:118-135: one loss per batch, averaged over ranks; val_loss = the unweighted mean over batches (what
+        MeanMetric over the gathered per-rank losses gives), val_ppl = exp(val_loss); logged, or printed without a tracker.
+        The masks are the evaluation masker's: the same at every evaluation."""
+        import math
+
+        model = self.model["model"]
+        was = model.training
+        model.eval()
+        try:
+            losses = [self._mean_over_ranks(self.forward_step(self._masked(batch, self.eval_masker, i)))
+                      for i, batch in enumerate(loader)]
+        finally:
+            model.train(was)
+        if not losses:
+            raise ValueError("the validation loader yields no batch (val_pct of the dataset does not fill eval_batch_size)")
+        val_loss = float(torch.stack(losses).mean())
+        metrics = {"val_loss": val_loss, "val_ppl": math.exp(val_loss)}
+        if self.config.train_args.wandb:
+            self.log(metrics, step=step)
+        elif self.rank == 0:
+            print(metrics, flush=True)
+        return metrics
+
+    def save_model(self, output_dir: str):
+        if self.rank == 0:
+            self.model["model"].save_pretrained(output_dir)
+
+    def save_state(self, output_dir: str):
+        """The layout of TextTextTrainer.save_state: model/, optimizer.pt, scheduler.pt, trainer_state.pt (the step, the mask
+        ordinal and the position in the epoch loop)."""
+        import os
+
+        os.makedirs(output_dir, exist_ok=True)
+        if self.rank == 0:
+            self.model["model"].save_pretrained(os.path.join(output_dir, "model"))
+            torch.save(self.optimizer.state_dict(), os.path.join(output_dir, "optimizer.pt"))
+            torch.save(self.scheduler.state_dict(), os.path.join(output_dir, "scheduler.pt"))
+            torch.save({"step": self.step, "ordinal": self.ordinal, "epoch": self.epoch, "batch_in_epoch": self.batch_in_epoch},
+                       os.path.join(output_dir, "trainer_state.pt"))
+        if self.world > 1:
+            dist.barrier()
+
+    def load_state(self, input_dir: str):
+        import os
+
+        from safetensors.torch import load_file
+
+        self.model["model"].load_reference_state_dict(load_file(os.path.join(input_dir, "model", "model.safetensors")))
+        self.optimizer.load_state_dict(torch.load(os.path.join(input_dir, "optimizer.pt"), map_location=self.device))
+        self.scheduler.load_state_dict(torch.load(os.path.join(input_dir, "scheduler.pt")))
+        st = torch.load(os.path.join(input_dir, "trainer_state.pt"))
+        self.step, self.ordinal = int(st["step"]), int(st["ordinal"])
+        self.epoch, self.batch_in_epoch = int(st["epoch"]), int(st["batch_in_epoch"])
+
+    def fit(self, loaders: dict, log_every: int = 0):
+        """The loop of sc/trainers/base.py:395-533 over the loaders of `get_mlm_loaders`: `num_epochs` epochs, curr_step =
+        epoch * len(train) + step, the LR horizon len(train) * num_epochs (micro-batches), evaluation every `eval_steps` optimizer
+        steps or after every epoch, `save_every` -> step_{curr_step}, per epoch epoch_{e}_model (+ epoch_{e} state when
+        num_epochs > 1), final_model at the end.  `train_args.checkpoint` -> load_state and resume at the saved epoch and batch:
+        the loader skips the batches already seen and the mask ordinal continues, so the resumed run sees the batches the
+        uninterrupted run would have.  Returns the per-micro-batch losses."""
+        import os
+
+        ta = self.config.train_args
+        train, val = loaders["train"], loaders.get("val")
+        if loaders.get("info") is not None:
+            self.attach_maskers(loaders["info"])
+        order = getattr(train, "batch_sampler", None)
+        per_epoch = int(getattr(order, "num_batches", 0) or len(train))
+        if self.step == 0:
+            self.set_total_steps(per_epoch * ta.num_epochs)
+        if ta.wandb and self.tracker is None:
+            from .trainers import TextTextTrainer
+
+            self.tracker = TextTextTrainer.get_trackers(self, self.config)
+        if ta.checkpoint:
+            self.load_state(ta.checkpoint)
+        start_epoch, start_batch = self.epoch, self.batch_in_epoch
+        if start_batch >= per_epoch:
+            start_epoch, start_batch = start_epoch + 1, 0
+        if (start_epoch, start_batch) != (0, 0) and not hasattr(order, "set_epoch"):
+            raise ValueError("resuming needs a loader whose batch sampler has set_epoch(epoch, start_batch)")
+        save_every = int(ta.save_every or 0)
+        out_dir = ta.output_dir
+        if save_every > 0 and not out_dir:
+            raise ValueError("train_args.save_every needs train_args.output_dir")
+        losses = []
+        curr_step = self.step
+        for epoch in range(start_epoch, ta.num_epochs):
+            first = start_batch if epoch == start_epoch else 0
+            if hasattr(order, "set_epoch"):
+                order.set_epoch(epoch, first)
+            for step, batch in enumerate(train, start=first):
+                curr_step = epoch * per_epoch + step
+                loss = self.training_step(self._masked(batch, self.masker, self.ordinal))
+                self.ordinal += 1
+                self.epoch, self.batch_in_epoch = epoch, step + 1
+                losses.append(loss)
+                if ta.wandb:   # base.py:485-502: the mean over ranks, every micro-step
+                    self.log({"loss": float(self._mean_over_ranks(loss))}, step=curr_step)
+                if log_every and (step + 1) % log_every == 0 and self.rank == 0:
+                    print(f"epoch {epoch} step {curr_step} loss {float(loss):.4f} lr {self.scheduler.get_last_lr()[0]:.3e}", flush=True)
+                if (val is not None and step > 0 and ta.eval_strategy == "steps" and ta.eval_steps and ta.eval_steps > 0
+                        and (step / self.accum) % ta.eval_steps == 0):
+                    self.eval_loop(val, curr_step)
+                if ta.wandb and step > 0 and ta.log_lr_every and step % ta.log_lr_every == 0:
+                    self.log({"lr": self.scheduler.get_last_lr()[0]}, step=curr_step)
+                if save_every > 0 and step > 0 and step % save_every == 0:
+                    self.save_state(os.path.join(out_dir, f"step_{curr_step}"))
+            if val is not None and ta.eval_strategy == "epochs":
+                self.eval_loop(val, curr_step)
+            if save_every > 0:
+                self.save_model(os.path.join(out_dir, f"epoch_{epoch}_model"))
+                if ta.num_epochs > 1:
+                    self.save_state(os.path.join(out_dir, f"epoch_{epoch}"))
+        if ta.num_epochs > 1 and save_every > 0:
+            if self.world > 1:
+                dist.barrier()
+            self.save_model(os.path.join(out_dir, "final_model"))
+        return losses
+
 
 def synthetic_mlm_batches(n_steps: int, batch: int, seq_len: int, vocab: int = 30522, mlm_probability: float = 0.3,
                           mask_token_id: int = 103, seed: int = 1234, ragged: bool = True) -> Iterable[dict]:

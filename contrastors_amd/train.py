@@ -8,6 +8,8 @@ available offline); otherwise `--synthetic-steps N` drives it with synthetic bat
 `--input_shards DIR --task_name rte` (a local directory with the task's splits) and runs its own epoch loop.
 `model_type: image_text` / `locked_text` with `data_args.image_text_shards` (local tar shards of image / caption pairs) and
 `--synthetic-steps 0` trains from contrastors_amd/image_data.py for `data_args.train_num_samples // batch_size` steps.
+`model_type: mlm` with `data_args.tokenized_dataset` (a LOCAL datasets `save_to_disk` directory or an (N, S) .npy) and
+`--synthetic-steps 0` runs `MLMTrainer.fit` over contrastors_amd/mlm_data.py: epochs, evaluation, checkpoints, resume.
 """
 from __future__ import annotations
 
@@ -134,6 +136,16 @@ def main():
         steps = config.data_args.train_num_samples // config.data_args.batch_size
         trainer.set_total_steps(steps)
         trainer.train(iter(loader), max_steps=steps, log_every=10)
+    elif config.model_args.model_type == "mlm" and args.synthetic_steps <= 0 and config.data_args.tokenized_dataset:
+        # sc/trainers/mlm.py:54-99 + the loop of base.py:395-533: a local pre-tokenized dataset, the workers read rows, the GPU
+        # draws the masks (contrastors_amd/mlm_data.py); evaluation, checkpoints and resume live in MLMTrainer.fit
+        from transformers import AutoTokenizer
+
+        from .mlm_data import MlmTokenInfo, get_mlm_loaders
+
+        tok = AutoTokenizer.from_pretrained(config.model_args.tokenizer_name, local_files_only=True)
+        rank = dist.get_rank() if world > 1 else 0
+        trainer.fit(get_mlm_loaders(config, MlmTokenInfo.from_tokenizer(tok), rank, world), log_every=10)
     elif args.synthetic_steps <= 0 and config.data_args.input_shards:
         from transformers import AutoTokenizer
 

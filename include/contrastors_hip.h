@@ -464,6 +464,24 @@ int cx_seqcls_head_bwd(const float* X, long ldx, const float* Wp, const float* W
 int cx_image_transform(const uint8_t* pixels, const int64_t* offsets, const int32_t* sizes, const int32_t* plan_i,
                        const double* plan_f, void* out, int out_bf16, int B, int S, const float* mean3, const float* std3,
                        void* stream);
+/* ---- masked-language-model masking on the device (transformers.DataCollatorForLanguageModeling.torch_mask_tokens, the collator
+ * of sc/trainers/mlm.py:70,84; contrastors_amd/mlm_data.py): ids (B, S) int32 (ids_i64 = 0) or int64 (ids_i64 = 1) with a row
+ * stride of ids_stride >= S elements -> out_ids, labels (B, S) int64, contiguous.  attention_mask (B, S) int64 and special_mask
+ * (B, S) uint8 are contiguous and may be NULL; special_ids is a DEVICE array of n_special <= 16 int64 token ids (NULL when 0).
+ * The token at flat position g = b * S + s takes one Philox4x32-10 call, counter (lo32(g), hi32(g), lo32(offset), hi32(offset)),
+ * key (lo32(seed), hi32(seed)) -> (u0, u1, u2, u3).  A token is special if its attention mask is 0, its special_mask is
+ * non-zero or its id is in special_ids.  A non-special token is a target iff u0 < T(p), T(x) = (uint32) fminf(x * 2^32,
+ * 4294967040.f); a target becomes mask_token_id iff u1 < T(0.8), else the word (uint64(u2) * random_vocab) >> 32 iff
+ * u1 < T(0.9), else keeps its id (u3 is unused).  labels = the original id at targets, -100 elsewhere; out_ids = ids at
+ * non-targets.  The result is a pure function of (seed, offset, g, id, specialness): not of the launch geometry, the dtype of
+ * ids or its stride; a repeated call gives the same bits.  random_vocab is len(tokenizer), not the padded model vocabulary.
+ * out_ids / labels must not overlap the inputs.  B or S < 1, n_special outside 0..16, random_vocab < 1, p outside [0, 1) or
+ * ids_stride < S: CX_ERR_SHAPE; a NULL ids / out_ids / labels (or special_ids with n_special > 0): CX_ERR_ARG.  Neither
+ * launches anything.  No allocation, no synchronisation.  Additive: cx_abi_version stays 10. */
+int cx_mlm_mask(const void* ids, int ids_i64, long ids_stride, const int64_t* attention_mask, const uint8_t* special_mask,
+                const int64_t* special_ids, int n_special, long mask_token_id, int random_vocab, float p,
+                unsigned long long seed, unsigned long long offset, int64_t* out_ids, int64_t* labels, int B, int S,
+                void* stream);
 /* ---- the same loss on the fp8 matrix-core path (BASELINE.json configs[4] "fp8 MFMA similarity GEMM"; the reference
  * only carries the `use_fp8` flag, configs/train/contrastive_pretrain.yaml:24).  Rows are quantised to OCP e4m3 with
  * one scale per row, the contraction is v_mfma_scale_f32_32x32x64_f8f6f4 (fp32 accumulate, online fp32 log-sum-exp);
