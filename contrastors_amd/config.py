@@ -114,11 +114,16 @@ class DataArgs(BaseModel):
     mask_on: str = "device"
     task_name: Optional[str] = None   # model_type: glue (sc/trainers/glue.py:50): cola, mnli, mrpc, qnli, qqp, rte, sst2, stsb
     # model_type: image_text / locked_text (sc/config.py:123-136 ImageTextDataArgs; contrastors_amd/image_data.py).  All inert
-    # unless image_text_shards is set; imagenet_val_path / eval_flickr parse and are not used (no zero-shot / Flickr evaluation)
+    # unless image_text_shards is set.  Evaluation (contrastors_amd/zeroshot.py): imagenet_val_path (an ImageFolder tree) is
+    # evaluated zero-shot when zeroshot_meta_path names the JSON with the class names / prompt templates; retrieval recall@k
+    # runs over the local tar shards of retrieval_eval_shards.  eval_flickr alone (the reference's hub download) parses and
+    # evaluates nothing: the trainer logs one warning that names retrieval_eval_shards
     image_text_shards: Optional[str] = None
     eval_batch_size: Optional[int] = None
     imagenet_val_path: Optional[str] = None
     eval_flickr: Optional[bool] = False
+    zeroshot_meta_path: Optional[str] = None
+    retrieval_eval_shards: Optional[str] = None
     train_num_samples: Optional[int] = None
     dataset_resampled: Optional[bool] = False
 

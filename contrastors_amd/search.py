@@ -161,8 +161,75 @@ class FlatIPIndex:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
 
+    def rank_batch_rows(self, row_ptr: torch.Tensor, nsplit: int = 0) -> int:
+        """The largest query batch (all rows, else halved down to a multiple of 128) whose cx_rank_ws_bytes -- for the batch
+        with the most targets -- fits the workspace bound.  row_ptr: the host CSR offsets (M + 1)."""
+        h = _C.lib()
+        M = row_ptr.numel() - 1
+        m = M
+        while m > 128:
+            starts = torch.arange(0, M, m)
+            nnz = int((row_ptr[torch.clamp(starts + m, max=M)] - row_ptr[starts]).max())
+            if h.cx_rank_ws_bytes(m, max(self.ntotal, 1), nnz, nsplit) <= self.workspace_bytes:
+                break
+            m = max(128, (m // 2) // 128 * 128)
+        return m
 
-MAX_CANDIDATES = 4096             # cx_rescore_topk's candidate-list bound
+    def rank(self, queries, targets, nsplit: int = 0):
+        """-> (ranks int64, scores float32, row_ptr int64): for every (query row, target id) entry the number of stored
+        vectors that come before the target in search()'s order (descending score, ties to the lower id) -- its 0-based
+        position, `search(...)[1][m, rank] == target` wherever rank < k -- and the target's score, with the bits search()
+        gives it (cx_rank_targets, csrc/rank.hip; the (M, ntotal) scores are never written).
+
+        targets: a length-M sequence of id lists (rows may be empty or repeat an id), a CSR pair (row_ptr (M + 1), ids), or a
+        1-D length-M integer tensor / array (one target per row: ranks and scores come back with shape (M,)).  Entries keep
+        the caller's order; row_ptr delimits the rows.  Ids outside [0, ntotal) raise before anything is launched.  numpy
+        queries -> numpy out, torch in -> torch out on the index's device.  nsplit has no effect on the result."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        q = _to_device_2d(queries, self.d, self.device)
+        M = q.shape[0]
+        if isinstance(targets, (torch.Tensor, np.ndarray)):
+            t = torch.as_tensor(targets).detach().cpu()
+            if t.dim() != 1 or t.numel() != M or t.dtype.is_floating_point or t.dtype == torch.bool:
+                raise ValueError(f"targets: expected {M} integer ids (one per query), got {tuple(t.shape)} {t.dtype}")
+            row_ptr, ids = torch.arange(M + 1, dtype=torch.int64), t.to(torch.int64)
+        else:
+            try:
+                row_ptr, ids = _exclusion_csr_host(targets, M)
+            except ValueError as e:
+                raise ValueError(str(e).replace("exclude", "targets")) from None
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal):
+            raise ValueError(f"targets: ids must lie in [0, {self.ntotal})")
+        nnz = ids.numel()
+        ranks = torch.zeros(nnz, dtype=torch.int32, device=self.device)
+        scores = torch.zeros(nnz, dtype=torch.float32, device=self.device)
+        if nnz and M:
+            h = _C.lib()
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                mb = self.rank_batch_rows(row_ptr, nsplit)
+                dptr, dids = row_ptr.to(self.device), ids.to(self.device)
+                D = self.vectors
+                ws = None
+                for b0 in range(0, M, mb):
+                    m = min(mb, M - b0)
+                    e0, e1 = int(row_ptr[b0]), int(row_ptr[b0 + m])
+                    if e1 == e0:
+                        continue
+                    nbytes = h.cx_rank_ws_bytes(m, self.ntotal, e1 - e0, nsplit)
+                    if ws is None or ws.numel() < nbytes:
+                        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                    bptr = dptr[b0: b0 + m + 1] - e0 if b0 else dptr   # offsets from 0 within the batch
+                    _C.check(h.cx_rank_targets(q[b0].data_ptr(), D.data_ptr(), m, self.ntotal, self.d, self.d, self.d,
+                                               bptr.data_ptr(), dids[e0:].data_ptr(), int(nsplit), ws.data_ptr(),
+                                               ranks[e0:].data_ptr(), scores[e0:].data_ptr(), stream), "cx_rank_targets")
+        ranks = ranks.to(torch.int64)
+        if as_numpy:
+            return ranks.cpu().numpy(), scores.cpu().numpy(), row_ptr.numpy()
+        return ranks, scores, row_ptr.to(self.device)
+
+
+MAX_CANDIDATES = 4096            # cx_rescore_topk's candidate-list bound
 
 
 def _check_code_dim(d: int) -> None:

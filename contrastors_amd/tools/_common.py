@@ -60,6 +60,24 @@ def encode_texts(texts: List[str], checkpoint: Optional[str], tokenizer_path: Op
     return encode(model, [prefix + t for t in texts], tok, batch_size=batch_size, max_length=max_length)
 
 
+def load_tower(checkpoint, device: str):
+    """A text or image BiEncoder from a local save_pretrained directory (config.json with the explicit trunk architecture)."""
+    from ..biencoder import BiEncoder, BiEncoderConfig
+    from ..nomic_bert import NomicBertConfig
+    from ..vit import ViTConfig
+
+    cfg = json.loads((Path(checkpoint) / "config.json").read_text())
+    kinds = {"NomicBertConfig": NomicBertConfig, "ViTConfig": ViTConfig}
+    if cfg.get("trunk_type") not in kinds:
+        raise SystemExit(f"error: {checkpoint}: trunk_type {cfg.get('trunk_type')!r} is not one of {sorted(kinds)}")
+    fields = {k: v for k, v in cfg.items() if k in BiEncoderConfig.__dataclass_fields__ and k != "trunk_config"}
+    kind = kinds[cfg["trunk_type"]]
+    fields["trunk_config"] = kind(**{k: v for k, v in cfg["trunk_config"].items() if k in kind.__dataclass_fields__})
+    model = BiEncoder(BiEncoderConfig(**fields), device=device)
+    model.load_pretrained(str(checkpoint))
+    return model
+
+
 COARSE = ("exact", "binary")
 ADD_ROWS = 1 << 18   # binary: document rows binarised per upload
 

@@ -136,6 +136,8 @@ def main():
         steps = config.data_args.train_num_samples // config.data_args.batch_size
         trainer.set_total_steps(steps)
         trainer.train(iter(loader), max_steps=steps, log_every=10)
+        if trainer.get_eval_data():   # sc/trainers/base.py:520-533: one evaluation at the end of training
+            trainer.eval_loop(trainer.step)
     elif config.model_args.model_type == "mlm" and args.synthetic_steps <= 0 and config.data_args.tokenized_dataset:
         # sc/trainers/mlm.py:54-99 + the loop of base.py:395-533: a local pre-tokenized dataset, the workers read rows, the GPU
         # draws the masks (contrastors_amd/mlm_data.py); evaluation, checkpoints and resume live in MLMTrainer.fit

@@ -505,7 +505,11 @@ class TextTextTrainer:
                     self.log({"lr": self.scheduler.get_last_lr()[0]}, step=self.step - 1)
             if log_every and (i + 1) % log_every == 0 and self.rank == 0:
                 print(f"step {self.step} loss {float(loss):.4f} lr {self.scheduler.get_last_lr()[0]:.3e}", flush=True)
+            self._after_training_step()
         return losses
+
+    def _after_training_step(self):
+        """Called by train() after every micro-step; nothing here (ImageTextTrainer evaluates every eval_steps)."""
 
 
 class ImageTextTrainer(TextTextTrainer):
@@ -515,13 +519,82 @@ class ImageTextTrainer(TextTextTrainer):
     Batches carry {"text": {...BiEncoder kwargs...}, "vision": {"input_ids": pixels (B,3,H,W)}} as in the reference."""
 
     def __init__(self, config: Config, dtype=torch.bfloat16, device=None, text_trunk_config=None,
-                 vision_trunk_config=None, total_steps: Optional[int] = None):
+                 vision_trunk_config=None, total_steps: Optional[int] = None, tokenizer=None):
         self._trunks = (text_trunk_config, vision_trunk_config)
         super().__init__(config, dtype=dtype, device=device, total_steps=total_steps)
         from .image_transform import GpuImageTransform   # sc/trainers/image_text.py:29-35 (the train transform; crops differ per rank)
 
         self.image_transform = GpuImageTransform.from_config(config.transforms, is_train=True, out_dtype=torch.bfloat16,
                                                              seed=config.data_args.seed + self.rank, device=self.device)
+        # evaluation (sc/trainers/image_text.py:93-126, 198-254; contrastors_amd/zeroshot.py): built on first use
+        self.tokenizer = tokenizer   # None: loaded from text_model_args.tokenizer_name when an evaluation needs it
+        self._eval_data = None
+        self.eval_image_transform = None
+        da = config.data_args
+        if da.eval_flickr and not da.retrieval_eval_shards:
+            import logging
+
+            logging.getLogger(__name__).warning(
+                "data_args.eval_flickr: the hub download of the Flickr test set is not available here and nothing is evaluated; "
+                "point data_args.retrieval_eval_shards at local tar shards of image + captions to get the recalls")
+
+    # ---- evaluation: zero-shot accuracy and retrieval recall@k (sc/trainers/image_text.py:93-126, 198-254) --------------
+    def get_eval_data(self) -> dict:
+        """{"imagenet": (ImageFolderDataset, meta)} when imagenet_val_path and zeroshot_meta_path are set, {"flickr":
+        RetrievalEvalDataset} when retrieval_eval_shards is; empty when the recipe names no evaluation data."""
+        if self._eval_data is None:
+            from .zeroshot import eval_data_from_config
+
+            self._eval_data = eval_data_from_config(self.config)
+        return self._eval_data
+
+    def _eval_tools(self):
+        from .image_transform import GpuImageTransform
+
+        if self.eval_image_transform is None:
+            self.eval_image_transform = GpuImageTransform.from_config(self.config.transforms, is_train=False,
+                                                                      out_dtype=torch.bfloat16, device=self.device)
+        if self.tokenizer is None:
+            from transformers import AutoTokenizer
+
+            self.tokenizer = AutoTokenizer.from_pretrained(self.config.text_model_args.tokenizer_name, local_files_only=True)
+        return self.eval_image_transform, self.tokenizer
+
+    def evaluate(self) -> dict:
+        """The metrics of one evaluation: top1_acc / top5_acc and flickr/<metric> for whichever data the recipe names.  The
+        classifier is rebuilt at every call (the text tower may be training).  Zero-shot runs on every rank over its share
+        of the images; retrieval on rank 0 alone, as in the reference."""
+        from .zeroshot import evaluate_from_config
+
+        data = self.get_eval_data()
+        if not data:
+            return {}
+        transform, tok = self._eval_tools()
+        return evaluate_from_config(self.model["model"], self.config, data, tok, transform, rank=self.rank, world=self.world)
+
+    def eval_loop(self, step):
+        """sc/trainers/image_text.py:198-254: evaluate and log through the tracker when train_args.wandb is set, else print on
+        rank 0.  -> the metrics."""
+        metrics = self.evaluate()
+        if not metrics:
+            return metrics
+        if getattr(self.config.train_args, "wandb", False):
+            self.log(metrics, step=step)
+        elif self.rank == 0:
+            acc = {k: v for k, v in metrics.items() if not k.startswith("flickr/")}
+            flickr = {k[len("flickr/"):]: v for k, v in metrics.items() if k.startswith("flickr/")}
+            if acc:
+                print(f"Step: {step} Top1: {acc['top1_acc']} Top5: {acc['top5_acc']}", flush=True)
+            if flickr:
+                print(f"Step: {step} Flickr: {flickr}", flush=True)
+        return metrics
+
+    def _after_training_step(self):
+        ta = self.config.train_args
+        if ta.eval_strategy != "steps" or not ta.eval_steps or ta.eval_steps <= 0:
+            return
+        if self.step % self.accum == 0 and (self.step // self.accum) % ta.eval_steps == 0 and self.get_eval_data():
+            self.eval_loop(self.step)
 
     # sc/trainers/image_text.py:53-68 + sc/models/dual_encoder/modeling_dual_encoder.py:10-24
     def get_model(self, config: Config, trunk_config=None) -> Dict[str, torch.nn.Module]:

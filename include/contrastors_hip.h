@@ -369,6 +369,18 @@ long cx_search_ws_bytes(int M, long N, int k, int nsplit);
 int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
                    const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, int nsplit, void* ws,
                    float* out_scores, int64_t* out_ids, void* stream);
+/* ---- rank of target columns in the rows of the similarity matrix (zero-shot top-k accuracy, retrieval recall@k:
+ *          sc/trainers/image_text.py:198-254; csrc/rank.hip).  Additive: cx_abi_version stays 10. ------------------------------
+ * Q, D, d, ldq, ldd, N: as cx_search_topk (same alignment rules and error codes).  tgt_ptr:(M+1) / tgt_ids: int64 CSR lists
+ * of target ids per query row (device memory; offsets from 0; ids in [0, N) -- the caller checks them before the call; a row
+ * may be empty or repeat an id).  For entry e of row m with t = tgt_ids[e]:  out_score[e] = s(m, t)  and
+ * out_rank[e] = #{ n in [0, N) : s(m,n) > s(m,t) or (s(m,n) == s(m,t) and n < t) }, the 0-based position of t in
+ * cx_search_topk's order, with the bits cx_search_topk gives s(m, t).  The (M,N) scores are never written.  The result does
+ * not depend on nsplit (<= 0: chosen); deterministic, no atomics.  ws: 16-B aligned, cx_rank_ws_bytes(M, N, nnz, nsplit)
+ * bytes with nnz = tgt_ptr[M], need not be initialised.  M == 0 or N == 0 launches nothing and succeeds. */
+long cx_rank_ws_bytes(int M, long N, long nnz, int nsplit);
+int cx_rank_targets(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const int64_t* tgt_ptr,
+                    const int64_t* tgt_ids, int nsplit, void* ws, int32_t* out_rank, float* out_score, void* stream);
 /* ---- binary (sign-bit) index with exact re-scoring (faiss IndexBinaryFlat, sentence-transformers "ubinary"; the recipes
  *          with `hamming: true`; csrc/search_binary.hip).  Additive: cx_abi_version stays 10. ---------------------------------
  * Sign codes: out:(rows, d/8) bytes, leading dimension ldo BYTES, in the layout of numpy.packbits(x > 0, axis=1) (dimension 0
