@@ -126,6 +126,10 @@ class DataArgs(BaseModel):
     retrieval_eval_shards: Optional[str] = None
     train_num_samples: Optional[int] = None
     dataset_resampled: Optional[bool] = False
+    # model_type: encoder (this path's key; contrastors_amd/retrieval_eval.py): a LOCAL directory in the BEIR on-disk layout
+    # (corpus.jsonl, queries.jsonl, qrels/test.tsv), or one with such a directory per task.  TextTextTrainer logs nDCG@10 per
+    # task as beir/<task> every train_args.eval_steps.  Nothing is downloaded; inert when unset
+    retrieval_eval_path: Optional[str] = None
 
     @model_validator(mode="after")
     def _mlm_keys(self):
@@ -183,6 +187,10 @@ class ModelArgs(BaseModel):
     resid_pdrop: Optional[float] = None
     ema: bool = False          # sc/config.py:179 + sc/trainers/base.py:387-391: an EMA copy of the weights, updated every step
     ema_decay: float = 0.9999  # (this path's key: the reference leaves the weighting as a TODO)
+    # sc/config.py:189-190: what the retrieval evaluation prepends to queries / documents (contrastors_amd/retrieval_eval.py)
+    # (a recipe may write null, as distill.yaml does: no prefix)
+    query_prefix: Optional[str] = "search_query: "
+    document_prefix: Optional[str] = "search_document: "
     patch_dropout: float = 0.0   # sc/config.py:180 -> PatchEmbedding's PatchDropout (image towers; sc/layers/embedding.py:415-418)
     # keys of the reference schema this path does not serve: accepted at their inert defaults, refused otherwise (a recipe
     # that sets them must not train as if it had not)

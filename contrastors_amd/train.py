@@ -95,6 +95,17 @@ def apply_overrides(config, overrides):
     return config
 
 
+def _final_eval(trainer):
+    """sc/trainers/base.py:520-533: one evaluation at the end of text-text training when the recipe names
+    data_args.retrieval_eval_path (the image-text branch above does its own; every other recipe does what it did)."""
+    from .trainers import ImageTextTrainer, TextTextTrainer
+
+    if not isinstance(trainer, TextTextTrainer) or isinstance(trainer, ImageTextTrainer):
+        return
+    if trainer.config.data_args.retrieval_eval_path and trainer.get_eval_data():
+        trainer.eval_loop(trainer.step)
+
+
 def main():
     args, overrides = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -158,6 +169,7 @@ def main():
             ds = get_streaming_dataset(config, tok, run_name=getattr(config.train_args, "wandb_run_name", None) or "run")
             trainer.set_total_steps(len(ds) // config.data_args.batch_size)  # before the first step: the LR horizon
             trainer.train(iter(ds), log_every=10)
+            _final_eval(trainer)
         else:  # sc/trainers/text_text.py:228-244: map-style dataset + DistributedSampler, per-rank batch
             from .data import get_local_dataloader
 
@@ -166,6 +178,7 @@ def main():
                                       add_prefix=config.model_args.add_prefix, num_workers=config.data_args.workers)
             trainer.set_total_steps(len(dl.dataset) // config.data_args.batch_size)
             trainer.train(iter(dl), log_every=10)
+            _final_eval(trainer)
     elif config.model_args.model_type == "mlm":
         from .mlm import synthetic_mlm_batches
 
@@ -175,6 +188,7 @@ def main():
                                             seed=1234 + rank), log_every=1)
     else:
         trainer.train(synthetic_batches(args.synthetic_steps, per_rank, args.seq_len, rank=trainer.rank), log_every=1)
+        _final_eval(trainer)
     if world > 1:
         dist.destroy_process_group()
 

@@ -4,8 +4,9 @@ sc/trainers/text_text.py:139-182,276-322,429-451 for the GradCache contrastive r
 Kept: the method set (`get_model`, `get_optimizer`, `get_scheduler`, `forward_step`, `backward`, `training_step`,
 `train`), the batch contract of the streaming loader (sc/dataset/text_text_loader.py:601-660: `query_input_ids`,
 `query_attention_mask`, `document_input_ids`, `document_attention_mask`, optional `dataset_name`) and the step order
-(clip -> optimizer -> scheduler -> zero_grad).  Not rebuilt: S3 shard streaming, wandb, NanoBEIR eval, checkpoints
-(out of the hot path): `train()` consumes any iterable of batches.
+(clip -> optimizer -> scheduler -> zero_grad).  Not rebuilt: S3 shard streaming, wandb, the NanoBEIR harness
+(out of the hot path): `train()` consumes any iterable of batches.  The validation number the reference
+takes from NanoBEIR -- nDCG@10 per task -- comes from a local BEIR-layout copy (data_args.retrieval_eval_path, retrieval_eval.py).
 """
 from __future__ import annotations
 
@@ -193,7 +194,7 @@ class JsonlTracker:
 
 class TextTextTrainer:
     def __init__(self, config: Config, dtype=torch.bfloat16, device=None, trunk_config: Optional[NomicBertConfig] = None,
-                 total_steps: Optional[int] = None):
+                 total_steps: Optional[int] = None, tokenizer=None):
         if dtype != torch.bfloat16:
             raise NotImplementedError("the native path computes in bf16 with fp32 master weights (--dtype=bf16)")
         self.accum = _accumulation_steps(config.train_args)
@@ -217,6 +218,9 @@ class TextTextTrainer:
         self.step = 0
         # sc/trainers/base.py:42-45,161-184: a tracker exists on rank 0 only, and only when the recipe asks for one
         self.tracker = self.get_trackers(config) if getattr(config.train_args, "wandb", False) else None
+        # retrieval evaluation (data_args.retrieval_eval_path): the tasks are read and the tokenizer loaded on first use
+        self.tokenizer = tokenizer   # None: loaded from model_args.tokenizer_name when an evaluation needs it
+        self._eval_data = None
         self._need_zero = True      # (gradient accumulation: the buffers are zeroed on the micro-step after an optimizer step)
         # sc/trainers/base.py:387-391: an EMA copy of the weights, updated after every training step
         if self._wants_ema(config):
@@ -508,8 +512,68 @@ class TextTextTrainer:
             self._after_training_step()
         return losses
 
+    # ---- evaluation: nDCG@10 per retrieval task (sc/trainers/text_text.py:243, 453-471; contrastors_amd/retrieval_eval.py) ----
+    def get_eval_data(self) -> dict:
+        """{task directory name: RetrievalTask} read from data_args.retrieval_eval_path (a local BEIR-layout directory, or one
+        with a directory per task), on rank 0 and on first use; empty when the recipe names none.  The other ranks get the
+        task names only: they wait while rank 0 evaluates."""
+        if self._eval_data is None:
+            path = self.config.data_args.retrieval_eval_path
+            if not path:
+                self._eval_data = {}
+            else:
+                from .retrieval_eval import find_tasks, load_beir_task
+
+                self._eval_data = {p.name: (load_beir_task(p) if self.rank == 0 else None) for p in find_tasks(path)}
+        return self._eval_data
+
+    def _eval_tokenizer(self):
+        if self.tokenizer is None:
+            from transformers import AutoTokenizer
+
+            self.tokenizer = AutoTokenizer.from_pretrained(self.config.model_args.tokenizer_name, local_files_only=True)
+        return self.tokenizer
+
+    def evaluate(self) -> dict:
+        """{"beir/<task>": nDCG@10, ..., "beir/mean"} of the model as it stands, on rank 0 ({} elsewhere and without evaluation
+        data); the other ranks wait at the barrier, as in the reference.  The model's training mode is restored."""
+        data = self.get_eval_data()
+        if not data:
+            return {}
+        metrics = {}
+        if self.rank == 0:
+            from .retrieval_eval import beir_log_metrics, evaluate_task
+
+            ma, da = self.config.model_args, self.config.data_args
+            tok = self._eval_tokenizer()
+            metrics = beir_log_metrics({name: evaluate_task(self.model["model"], tok, task, ks=(10,), query_prefix=ma.query_prefix or "",
+                                                            document_prefix=ma.document_prefix or "", max_length=ma.seq_len,
+                                                            batch_size=da.eval_batch_size or 256)
+                                        for name, task in data.items()})
+        if self.distributed and self.world > 1:
+            dist.barrier()
+        return metrics
+
+    def eval_loop(self, step):
+        """sc/trainers/text_text.py:453-471: evaluate and log through the tracker when train_args.wandb is set, else print on
+        rank 0.  -> the metrics."""
+        metrics = self.evaluate()
+        if not metrics:
+            return metrics
+        if getattr(self.config.train_args, "wandb", False):
+            self.log(metrics, step=step)
+        elif self.rank == 0:
+            print(f"Step: {step} {metrics}", flush=True)
+        return metrics
+
     def _after_training_step(self):
-        """Called by train() after every micro-step; nothing here (ImageTextTrainer evaluates every eval_steps)."""
+        """Called by train() after every micro-step: with eval_strategy "steps", one evaluation every eval_steps optimizer steps
+        when the recipe names evaluation data; nothing otherwise."""
+        ta = self.config.train_args
+        if ta.eval_strategy != "steps" or not ta.eval_steps or ta.eval_steps <= 0:
+            return
+        if self.step % self.accum == 0 and (self.step // self.accum) % ta.eval_steps == 0 and self.get_eval_data():
+            self.eval_loop(self.step)
 
 
 class ImageTextTrainer(TextTextTrainer):

@@ -381,6 +381,23 @@ int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, l
 long cx_rank_ws_bytes(int M, long N, long nnz, int nsplit);
 int cx_rank_targets(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const int64_t* tgt_ptr,
                     const int64_t* tgt_ids, int nsplit, void* ws, int32_t* out_rank, float* out_score, void* stream);
+/* ---- retrieval metrics from target ranks (nDCG / MAP / recall / precision / MRR / hit rate at K cut-offs; trec_eval's
+ *          ndcg_cut, map_cut, recall, P and BEIR's MRR; csrc/ir_metrics.hip).  Additive: cx_abi_version stays 10. -------------
+ * row_ptr:(M+1) int64 offsets from 0, ranks / gains:(nnz) -- device memory, the CSR rows of cx_rank_targets with the ranks
+ * widened to int64.  An entry with gain > 0 is a relevant document of that (linear) gain; an entry with gain == 0 is an
+ * EXCLUDED document: it is taken out of the ranking.  Ranks within a row are distinct.  With R = the relevant entries of a row,
+ *   a_j = rank_j - #{excluded e : rank_e < rank_j},  before_j = #{relevant i : a_i < a_j},
+ *   ipos_j = #{relevant i : gain_i > gain_j or (gain_i == gain_j and i < j)},
+ * and for cut-off k = ks[c] (ks: HOST memory, K in [1, 8], every k >= 1), out:(M, K, 6) double holds
+ *   ndcg = sum_{a_j<k} gain_j / log2(a_j + 2) / sum_{ipos_j<k} gain_j / log2(ipos_j + 2),  ap = (1/R) sum_{a_j<k} (before_j + 1) / (a_j + 1),
+ *   recall = hits / R,  precision = hits / k,  rr = 1 / (min_j a_j + 1) if that minimum is < k else 0,  hit = hits > 0,
+ * hits = #{a_j < k}; nrel:(M) int = R.  A row with R == 0 gives zeros; a row of more than CX_IR_MAX_ROW entries is not staged:
+ * it gives NaNs and nrel = -1.  fp64 sums in a fixed order, no atomics: bitwise reproducible.  One workgroup per row.
+ * CX_ERR_SHAPE: K outside [1, 8], a k < 1, M < 0; CX_ERR_ARG: a null pointer (ks is looked at first); M == 0 launches nothing. */
+#define CX_IR_MAX_ROW 4096
+#define CX_IR_MAX_K 8
+int cx_ir_metrics(const int64_t* row_ptr, const int64_t* ranks, const float* gains, int M, const int* ks, int K, double* out,
+                  int* nrel, void* stream);
 /* ---- binary (sign-bit) index with exact re-scoring (faiss IndexBinaryFlat, sentence-transformers "ubinary"; the recipes
  *          with `hamming: true`; csrc/search_binary.hip).  Additive: cx_abi_version stays 10. ---------------------------------
  * Sign codes: out:(rows, d/8) bytes, leading dimension ldo BYTES, in the layout of numpy.packbits(x > 0, axis=1) (dimension 0
