@@ -344,7 +344,8 @@ int cx_pool_normalize_bwd(const float* demb, const float* emb, const float* norm
  * labels:(N) int64 = (arange(N)+rank*N)*(G/(N*world)) computed by the host exactly as loss.py:108-117.
  * logits = scale * Q D^T are never written: exact-fp32 MFMA tiles feed an online row log-sum-exp.
  * ws: fp32 scratch of cx_infonce_ws_floats(N,G) floats.  Outputs: lse:(N) fp32, loss_rows:(N) fp32
- * (= lse_i - logit_{i,label_i}); the host takes mean * world_size (loss.py:125). */
+ * (= lse_i - logit_{i,label_i}); the host takes mean * world_size (loss.py:125).  Every label must lie in [0, G): a label
+ * outside it leaves that row's positive logit unwritten in ws and its loss_rows undefined (lse and the arg max do not read it). */
 long cx_infonce_ws_floats(int N, int G);
 int cx_infonce_fwd(const float* Q, const float* D, const int64_t* labels, float scale, float* ws, float* lse,
                    float* loss_rows, int N, int G, int dim, int ldq, int ldd, void* stream);
@@ -528,7 +529,9 @@ int cx_infonce_fp8_bwd(const float* Q, const float* D, const int64_t* labels, co
                        const uint8_t* Q8, const uint8_t* D8, const float* sq, const float* sd, uint16_t* GmT, uint16_t* Qb,
                        uint16_t* QbT, uint16_t* Db, float* gws, long gws_floats, float* dQ, float* dD,
                        float* dscale_accum, int N, int G, int dim, int ldq, int ldd, void* stream);
-/* plain exact-fp32 MFMA GEMM  C[m][n] = sum_k A[m][k] B[n][k]  (K % 4 == 0; lda, ldb % 4 == 0). */
+/* plain exact-fp32 MFMA GEMM  C[m][n] = sum_k A[m][k] B[n][k]  (K % 4 == 0; lda, ldb % 4 == 0).  Each element has the bits of
+ * the fp32 fmaf chain from +0 over k in blocks of 16, inside a block in the order 0 4 1 5 2 6 3 7 8 12 9 13 10 14 11 15; the
+ * zero-filled steps of a K tail (K % 16 != 0) add +0, so a sum that underflows to -0 comes out as +0 there. */
 int cx_sgemm_nt(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
                 void* stream);
 int cx_transpose_f32(const float* In, float* Out, int rows, int cols, int ld_in, int ld_out, void* stream);
