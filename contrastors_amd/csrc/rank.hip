@@ -23,19 +23,12 @@
 //      on neither nsplit nor scheduling, and no atomic is involved.
 // No candidate lists, no merge, no k, no fp32 score tile in LDS.
 #include "cx_common.h"
+#include "score_tile.h"   // TM / TN / BK / PANEL, poff, tile_scores, auto_splits: shared with range.hip
 #include "../../include/contrastors_hip.h"
 
 namespace {
 
-constexpr int TM = 128, TN = 128, BK = 64;
-constexpr int PANEL = TM * BK * 2;   // 16 KiB: one operand's 64-wide K chunk, 128 rows x 128 B
-constexpr int MAXSPLIT = 64;
-constexpr long MAX_N = 0x7fffffffL - TN;   // int column indices of the last tile (as search.hip)
-constexpr int SPLIT_TARGET_WG = 512;
 constexpr int PGMAX = 8;
-
-// [128 rows][8 chunks of 16 B]: chunk c of row r at r*128 + ((c ^ (r & 7)) << 4)  (search.hip's layout)
-CX_DEVICE int poff(int r, int c) { return r * 128 + ((c ^ (r & 7)) << 4); }
 
 struct RankParams {
     const bf16_t* Q;
@@ -49,60 +42,6 @@ struct RankParams {
     int32_t* out_rank;
     float* out_score;
 };
-
-// search.hip's tile: acc[a][b][r] = score(query row qrow(a), document row drow(b, r)) of the 128 x 128 tile whose query rows
-// start at element offsets qo[i] and document rows at do_[i] (i: this thread's four staging rows tid/8 + 32 i).
-CX_DEVICE void tile_scores(const bf16_t* Q, const bf16_t* D, const int64_t (&qo)[4], const int64_t (&do_)[4], int nk, char* ops,
-                           int tid, f32x4_t (&acc)[4][4]) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
-    const int c8 = (tid & 7) * 8;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    uint4 sq[4], sd[4];
-    auto stage = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            sq[i] = *reinterpret_cast<const uint4*>(Q + qo[i] + k0 + c8);
-            sd[i] = *reinterpret_cast<const uint4*>(D + do_[i] + k0 + c8);
-        }
-    };
-    auto commit = [&](char* qbuf, char* dbuf) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = (tid >> 3) + 32 * i, c = tid & 7;
-            *reinterpret_cast<uint4*>(qbuf + poff(r, c)) = sq[i];
-            *reinterpret_cast<uint4*>(dbuf + poff(r, c)) = sd[i];
-        }
-    };
-    stage(0);
-    commit(ops, ops + PANEL);
-    __syncthreads();
-    for (int kc = 0; kc < nk; ++kc) {
-        const char* qb_ = ops + (kc & 1) * 2 * PANEL;
-        const char* db_ = qb_ + PANEL;
-        stage(min(kc + 1, nk - 1) * BK);   // the last chunk is staged twice, as in search.hip
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8_t fq[4], fd[4];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                fq[b] = *reinterpret_cast<const bf16x8_t*>(qb_ + poff(wq * 64 + b * 16 + l15, ks * 4 + lh));
-                fd[b] = *reinterpret_cast<const bf16x8_t*>(db_ + poff(wd * 64 + b * 16 + l15, ks * 4 + lh));
-            }
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[b], fq[a], acc[a][b], 0, 0, 0);
-        }
-        char* nq = ops + ((kc + 1) & 1) * 2 * PANEL;   // read last in chunk kc - 1, behind the barrier below
-        commit(nq, nq + PANEL);
-        __syncthreads();
-    }
-}
 
 struct GatherLds {
     char ops[4 * PANEL];
@@ -273,14 +212,6 @@ __global__ __launch_bounds__(256) void rank_sum_kernel(const int64_t* __restrict
         for (int i = 0; i < 2 * nsplit; ++i) c += part[e * 2 * nsplit + i];
         out_rank[e] = c;
     }
-}
-
-int auto_splits(int M, long N, int nsplit) {
-    const int tiles_m = (M + TM - 1) / TM;
-    const long tiles_n = (N + TN - 1) / TN;
-    if (nsplit <= 0) nsplit = (SPLIT_TARGET_WG + tiles_m - 1) / tiles_m;
-    nsplit = min(nsplit, MAXSPLIT);
-    return (int)max(1L, min((long)nsplit, tiles_n));
 }
 
 }  // namespace

@@ -4,7 +4,10 @@
 (scripts/text/index_filtering.py:364-377, scripts/text/get_negatives.py:163-168): same method names (`add`, `search`,
 `ntotal`, `reset`), bf16 storage, one fused HIP kernel per query batch (csrc/search.hip, cx_search_topk) that never writes
 the (queries x corpus) scores.  `search` adds what the margin miner needs on top of faiss: per-row excluded ids (the
-positives) and a per-row exclusive score bound (margin * s(q, pos)).
+positives) and a per-row exclusive score bound (margin * s(q, pos)).  `rank` gives the position of given ids in that order
+(csrc/rank.hip); `range_count` / `range_search` answer "which rows score above a threshold", however many there are -- faiss's
+`range_search`, which faiss has on the CPU only (csrc/range.hip; near-duplicate removal and decontamination on top of it are
+in contrastors_amd/dedup.py).
 
 `BinaryFlatIndex` is the same surface over sign codes (faiss `IndexBinaryFlat`, d / 8 bytes per vector) for the recipes
 trained with `hamming: true`; `rescore` / `search_binary_rescored` re-score its candidates exactly against the bf16 rows,
@@ -227,6 +230,118 @@ class FlatIPIndex:
         if as_numpy:
             return ranks.cpu().numpy(), scores.cpu().numpy(), row_ptr.numpy()
         return ranks, scores, row_ptr.to(self.device)
+
+    def range_batch_rows(self, M: int, nsplit: int = 0) -> int:
+        """The largest query batch (all of M, else halved down to a multiple of 128) whose cx_range_ws_bytes fits the bound."""
+        h = _C.lib()
+        m = M
+        while m > 128 and h.cx_range_ws_bytes(m, max(self.ntotal, 1), nsplit) > self.workspace_bytes:
+            m = max(128, (m // 2) // 128 * 128)
+        return m
+
+    def _range_bounds(self, radius, min_id, M: int):
+        """radius (a scalar or M values) and min_id (None or M ids) -> device tensors (M,) float32 and (M,) int64 / None."""
+        if isinstance(radius, (int, float)):
+            rad = torch.full((M,), float(radius), dtype=torch.float32, device=self.device)
+        else:
+            rad = torch.as_tensor(np.asarray(radius) if not isinstance(radius, torch.Tensor) else radius)
+            rad = rad.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+            if rad.numel() == 1 and M != 1:
+                rad = rad.expand(M).contiguous()
+            if rad.numel() != M:
+                raise ValueError(f"radius has {rad.numel()} entries for {M} queries")
+        mid = None
+        if min_id is not None:
+            mid = torch.as_tensor(np.asarray(min_id) if not isinstance(min_id, torch.Tensor) else min_id)
+            if mid.dtype.is_floating_point or mid.dtype == torch.bool:
+                raise ValueError(f"min_id: expected integer ids, got {mid.dtype}")
+            mid = mid.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+            if mid.numel() != M:
+                raise ValueError(f"min_id has {mid.numel()} entries for {M} queries")
+        return rad, mid
+
+    def _range_batches(self, q, rad, mid, nsplit: int):
+        """Per query batch, after its cx_range_count: (b0, m, the C-ABI arguments shared with cx_range_emit (Q .. ws), counts
+        (m,) int64).  One workspace serves all batches: a batch's emit must be launched before the next batch is drawn."""
+        h = _C.lib()
+        M = q.shape[0]
+        mb = self.range_batch_rows(M, nsplit)
+        last = M - (M - 1) // mb * mb
+        nbytes = max(h.cx_range_ws_bytes(mb, self.ntotal, nsplit), h.cx_range_ws_bytes(last, self.ntotal, nsplit))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        D = self.vectors
+        stream = _C.cur_stream()
+        for b0 in range(0, M, mb):
+            m = min(mb, M - b0)
+            args = (q[b0].data_ptr(), D.data_ptr(), m, self.ntotal, self.d, self.d, self.d, rad[b0:].data_ptr(),
+                    None if mid is None else mid[b0:].data_ptr(), int(nsplit), ws.data_ptr())
+            counts = torch.empty(m, dtype=torch.int64, device=self.device)
+            _C.check(h.cx_range_count(*args, counts.data_ptr(), stream), "cx_range_count")
+            yield b0, m, args, counts
+
+    def range_count(self, queries, radius, min_id=None, nsplit: int = 0):
+        """-> counts (M,) int64: per query the number of stored vectors n with score > radius (strict) and n > min_id
+        (cx_range_count, csrc/range.hip; the (M, ntotal) scores are never written).  radius: a scalar or M values (NaN admits
+        nothing, -inf every finite score); min_id: None (= -1) or M ids.  numpy in -> numpy out, torch in -> torch out on
+        the index's device.  nsplit has no effect on the result."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        q = _to_device_2d(queries, self.d, self.device)
+        M = q.shape[0]
+        rad, mid = self._range_bounds(radius, min_id, M)
+        counts = torch.zeros(M, dtype=torch.int64, device=self.device)
+        if M and self.ntotal:
+            with torch.cuda.device(self.device):
+                for b0, m, _, c in self._range_batches(q, rad, mid, nsplit):
+                    counts[b0: b0 + m] = c
+        return counts.cpu().numpy() if as_numpy else counts
+
+    def range_search(self, queries, radius, min_id=None, max_results: int = 1 << 27, nsplit: int = 0):
+        """-> (lims (M + 1) int64, scores (nnz) float32, ids (nnz) int64), faiss's range_search layout: the stored vectors
+        with score > radius[m] (strict) and id > min_id[m] of query m are entries lims[m] : lims[m + 1], in ascending id
+        order, with the score bits search() gives the pair.  However many there are: nothing is cut at a k.
+
+        Per query batch the kernel counts first (cx_range_count); the total is read on the host and a running total above
+        max_results raises ValueError BEFORE the batch's results are allocated; only then cx_range_emit writes them (not
+        launched for a batch without results).  radius, min_id, nsplit: as range_count.  min_id = the queries' own corpus
+        ids turns a self-join into every unordered pair once.  numpy in -> numpy out, torch in -> torch out."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        q = _to_device_2d(queries, self.d, self.device)
+        M = q.shape[0]
+        rad, mid = self._range_bounds(radius, min_id, M)
+        max_results = int(max_results)
+        lims = torch.zeros(M + 1, dtype=torch.int64, device=self.device)
+        out_s, out_i = [], []
+        total = 0
+        if M and self.ntotal:
+            h = _C.lib()
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                for b0, m, args, counts in self._range_batches(q, rad, mid, nsplit):
+                    blims = torch.zeros(m + 1, dtype=torch.int64, device=self.device)
+                    torch.cumsum(counts, 0, out=blims[1:])
+                    n = int(blims[-1])   # (the host waits for the count pass here)
+                    if total + n > max_results:
+                        raise ValueError(f"range_search: {total + n} results after {b0 + m} of {M} queries exceed "
+                                         f"max_results = {max_results}; raise the radius or max_results")
+                    lims[b0 + 1: b0 + m + 1] = blims[1:] + total
+                    total += n
+                    if n == 0:
+                        continue
+                    s = torch.empty(n, dtype=torch.float32, device=self.device)
+                    i = torch.empty(n, dtype=torch.int64, device=self.device)
+                    _C.check(h.cx_range_emit(*args, blims.data_ptr(), s.data_ptr(), i.data_ptr(), stream), "cx_range_emit")
+                    out_s.append(s)
+                    out_i.append(i)
+        if len(out_s) == 1:
+            scores, ids = out_s[0], out_i[0]
+        elif out_s:
+            scores, ids = torch.cat(out_s), torch.cat(out_i)
+        else:
+            scores = torch.empty(0, dtype=torch.float32, device=self.device)
+            ids = torch.empty(0, dtype=torch.int64, device=self.device)
+        if as_numpy:
+            return lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
+        return lims, scores, ids
 
 
 MAX_CANDIDATES = 4096            # cx_rescore_topk's candidate-list bound

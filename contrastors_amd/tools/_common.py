@@ -16,7 +16,8 @@ def triplet_metadata(query_key: str, document_key: str, negatives_key: str) -> d
 
 
 def write_shards(records: List[dict], output_dir, metadata: dict, shard_size: int = SHARD_SIZE) -> List[Path]:
-    """Every record gets `metadata`; shard-00000.jsonl.gz, ... of `shard_size` records each (the reference's writer)."""
+    """Every record gets `metadata` (None: the records keep their own); shard-00000.jsonl.gz, ... of `shard_size` records
+    each (the reference's writer)."""
     out = Path(output_dir)
     out.mkdir(parents=True, exist_ok=True)
     paths = []
@@ -24,7 +25,8 @@ def write_shards(records: List[dict], output_dir, metadata: dict, shard_size: in
         p = out / f"shard-{start // shard_size:05d}.jsonl.gz"
         with gzip.open(p, "wt") as f:
             for rec in records[start: start + shard_size]:
-                rec["metadata"] = metadata
+                if metadata is not None:
+                    rec["metadata"] = metadata
                 f.write(json.dumps(rec) + "\n")
         paths.append(p)
     return paths

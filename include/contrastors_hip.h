@@ -382,6 +382,26 @@ int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, l
 long cx_rank_ws_bytes(int M, long N, long nnz, int nsplit);
 int cx_rank_targets(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const int64_t* tgt_ptr,
                     const int64_t* tgt_ids, int nsplit, void* ws, int32_t* out_rank, float* out_score, void* stream);
+/* ---- exact range search: every document above a per-row bound (faiss IndexFlatIP.range_search; near-duplicate removal,
+ *          decontamination, per-row radius queries; csrc/range.hip).  Additive: cx_abi_version stays 10. ----------------------
+ * Q, D, d, ldq, ldd, N: as cx_search_topk (same alignment rules and error codes).  radius:(M) fp32, min_id:(M) int64 or NULL
+ * (= -1 everywhere), device memory.  Row m admits document n iff s(m,n) > radius[m] (strict) and n > min_id[m], with the bits
+ * cx_search_topk gives s(m,n); a NaN radius admits nothing, -inf every finite score.  The (M,N) scores are never written.
+ * cx_range_count: counts:(M) int64 = the number of admitted n per row; it also leaves in ws what cx_range_emit needs (partial
+ * counts per corpus split, one flag per (query tile, corpus tile) that holds an admitted pair).  Corpus tiles that end at or
+ * below the smallest min_id of a 128-row query tile are not computed.
+ * cx_range_emit: same arguments, same nsplit, ws as cx_range_count left it; lims:(M+1) int64 = the exclusive prefix sum of
+ * counts (computed by the caller, who can refuse the total first).  Row m's admitted (score, id) pairs go to
+ * out_scores / out_ids [lims[m], lims[m+1]) in ASCENDING id order; unflagged tiles are not recomputed.
+ * Neither result depends on nsplit (<= 0: chosen), on query batching or on scheduling; deterministic, no global atomics.
+ * ws: 16-B aligned, cx_range_ws_bytes(M, N, nsplit) bytes, need not be initialised.  M == 0 or N == 0 launches nothing and
+ * succeeds. */
+long cx_range_ws_bytes(int M, long N, int nsplit);
+int cx_range_count(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const float* radius,
+                   const int64_t* min_id, int nsplit, void* ws, int64_t* counts, void* stream);
+int cx_range_emit(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const float* radius,
+                  const int64_t* min_id, int nsplit, const void* ws, const int64_t* lims, float* out_scores, int64_t* out_ids,
+                  void* stream);
 /* ---- retrieval metrics from target ranks (nDCG / MAP / recall / precision / MRR / hit rate at K cut-offs; trec_eval's
  *          ndcg_cut, map_cut, recall, P and BEIR's MRR; csrc/ir_metrics.hip).  Additive: cx_abi_version stays 10. -------------
  * row_ptr:(M+1) int64 offsets from 0, ranks / gains:(nnz) -- device memory, the CSR rows of cx_rank_targets with the ranks
