@@ -189,6 +189,9 @@ _SIGS = {
     "cx_range_ws_bytes": (i64, [i32, i64, i32]),
     "cx_range_count": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, i32, vp, vp, vp]),
     "cx_range_emit": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "cx_kmeans_assign": (i32, [vp, vp, vp, i64, i64, i32, i64, i64, vp, vp, vp, vp]),
+    "cx_kmeans_partial": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
+    "cx_kmeans_finish": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, vp, vp]),
     "cx_ir_metrics": (i32, [vp, vp, vp, i32, C.POINTER(i32), i32, vp, vp, vp]),
     "cx_pack_sign_bits": (i32, [vp, i32, i64, i32, i64, vp, i64, vp]),
     "cx_search_hamming_ws_bytes": (i64, [i32, i64, i32, i32]),

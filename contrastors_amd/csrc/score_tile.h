@@ -1,5 +1,6 @@
 // score_tile.h -- the 128 x 128 MFMA score tile of the kernels that walk (query tile x corpus split) without keeping
-// candidates: rank.hip (the rank of target columns) and range.hip (every column above a per-row bound).
+// candidates: rank.hip (the rank of target columns), range.hip (every column above a per-row bound) and kmeans.hip (the arg-max
+// over a centroid table, walked whole by one workgroup).
 //
 // Scores have search.hip's instruction sequence: v_mfma_f32_16x16x32_bf16 with A := document rows, B := query rows, K
 // ascending in 32-wide steps from a zero fp32 accumulator.  An output element of that instruction depends on its own A row

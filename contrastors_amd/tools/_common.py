@@ -32,11 +32,12 @@ def write_shards(records: List[dict], output_dir, metadata: dict, shard_size: in
     return paths
 
 
-def load_npy(path, n: int, what: str, mmap: bool = False) -> np.ndarray:
-    """mmap: map the file instead of reading it (the binary coarse search only ever gathers candidate rows from it)."""
+def load_npy(path, n: Optional[int], what: str, mmap: bool = False) -> np.ndarray:
+    """mmap: map the file instead of reading it (the binary coarse search only ever gathers candidate rows from it).
+    n = None: any number of rows."""
     x = np.load(path, mmap_mode="r" if mmap else None)
-    if x.ndim != 2 or x.shape[0] != n:
-        raise SystemExit(f"error: {what} embeddings {path} have shape {x.shape}, expected ({n}, d)")
+    if x.ndim != 2 or (n is not None and x.shape[0] != n):
+        raise SystemExit(f"error: {what} embeddings {path} have shape {x.shape}, expected ({'n' if n is None else n}, d)")
     return x
 
 

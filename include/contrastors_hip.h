@@ -402,6 +402,30 @@ int cx_range_count(const uint16_t* Q, const uint16_t* D, int M, long N, int d, l
 int cx_range_emit(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const float* radius,
                   const int64_t* min_id, int nsplit, const void* ws, const int64_t* lims, float* out_scores, int64_t* out_ids,
                   void* stream);
+/* ---- k-means over bf16 points: fused assignment and a deterministic centroid update (cluster-scoped curation, clustering
+ *          evaluation, coarse quantisers; csrc/kmeans.hip).  Additive: cx_abi_version stays 10. ------------------------------
+ * cx_kmeans_assign: X:(N,d) ldx points, C:(K,d) ldc centroids (alignment rules and d as cx_search_topk; N, K <= 2^31 - 129,
+ * K >= 1), half_norm:(K) fp32 or NULL.  Per point: label = argmax_c s(x,c) - half_norm[c] (ties to the lower c), best = that
+ * value, second:(N) or NULL = the second largest value (-inf for K == 1).  s(x,c) has the bits cx_search_topk gives the pair
+ * (X as queries, C as corpus); the bias is subtracted once, in fp32.  No workspace.  N == 0 launches nothing and succeeds.
+ * cx_kmeans_partial / cx_kmeans_finish: the update, from a plan the caller builds on the device.  order:(N) int32 = the point
+ * ids sorted by label, stable (a cluster is a run of ascending ids); the runs are cut into PIECES of at most
+ * CX_KMEANS_PIECE_ROWS entries: piece_start / piece_end:(max_pieces) int32 offsets into order, in run order; piece_ptr:(K+1)
+ * int32 = cluster k owns pieces piece_ptr[k] : piece_ptr[k+1]; n_pieces:(1) int32 on the device = piece_ptr[K].  The grids are
+ * sized by max_pieces >= n_pieces (ceil(N / CX_KMEANS_PIECE_ROWS) + K always is); workgroups past n_pieces exit.
+ * partial:(max_pieces,d) fp32: row p = the sum of piece p's rows of X.  cx_kmeans_finish adds a cluster's partials in piece order
+ * and writes counts:(K) int32, centroids:(K,d) fp32 (the mean; spherical != 0: the sum scaled to unit L2 norm), shadow:(K,d) lds
+ * = the centroid rounded to bf16, half_norm:(K) = |shadow|^2 / 2 in fp32, summed over ascending dimension (spherical: 0).  An
+ * empty cluster gets count 0 and keeps its centroid, shadow and half_norm.  No atomics: the summation order is a function of the
+ * labels, N and d only, the result bitwise reproducible. */
+#define CX_KMEANS_PIECE_ROWS 256
+int cx_kmeans_assign(const uint16_t* X, const uint16_t* C, const float* half_norm, long N, long K, int d, long ldx, long ldc,
+                     int32_t* label, float* best, float* second, void* stream);
+int cx_kmeans_partial(const uint16_t* X, long N, int d, long ldx, const int32_t* order, const int32_t* piece_start,
+                      const int32_t* piece_end, const int32_t* n_pieces, int max_pieces, float* partial, void* stream);
+int cx_kmeans_finish(const float* partial, const int32_t* piece_start, const int32_t* piece_end, const int32_t* piece_ptr, long K,
+                     int d, int max_pieces, int spherical, int32_t* counts, float* centroids, uint16_t* shadow, long lds,
+                     float* half_norm, void* stream);
 /* ---- retrieval metrics from target ranks (nDCG / MAP / recall / precision / MRR / hit rate at K cut-offs; trec_eval's
  *          ndcg_cut, map_cut, recall, P and BEIR's MRR; csrc/ir_metrics.hip).  Additive: cx_abi_version stays 10. -------------
  * row_ptr:(M+1) int64 offsets from 0, ranks / gains:(nnz) -- device memory, the CSR rows of cx_rank_targets with the ranks
