@@ -189,6 +189,9 @@ _SIGS = {
     "cx_range_ws_bytes": (i64, [i32, i64, i32]),
     "cx_range_count": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, i32, vp, vp, vp]),
     "cx_range_emit": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "cx_range_window_ws_bytes": (i64, [i32, i64, i64, i32]),
+    "cx_range_window_count": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
+    "cx_range_window_emit": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
     "cx_kmeans_assign": (i32, [vp, vp, vp, i64, i64, i32, i64, i64, vp, vp, vp, vp]),
     "cx_kmeans_partial": (i32, [vp, i64, i32, i64, vp, vp, vp, vp, i32, vp, vp]),
     "cx_kmeans_finish": (i32, [vp, vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, i64, vp, vp]),

@@ -4,10 +4,15 @@ The standard recipe: take ALL pairs of corpus rows with cosine above a threshold
 in query batches -- a duplicate cluster of any size comes back whole, which a top-k search cannot promise), group them
 (`components`) and keep one row per group (`select_kept`); and drop training rows that sit within a threshold of any
 evaluation row (`contaminated`).  The GPU work goes through the index; the graph logic is host numpy.
+
+Past the sizes an O(N^2 d) self-join can serve, the pairs are sought inside the parts of a partition -- k-means labels
+(SemDeDup), or any partition a curator already has: `cluster_plan` sorts the rows by label, `clustered_duplicate_edges` runs
+one windowed self-join per chunk of whole clusters (min_id = own position, end_id = the cluster's end: only the block-diagonal
+band of the sorted corpus is computed), and `edge_recall` estimates on a sample of rows what the partition lost.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import List, Tuple
 
 import numpy as np
 import torch
@@ -44,6 +49,101 @@ def duplicate_edges(index, threshold: float, batch_rows: int = DEFAULT_BATCH_ROW
     if not src:
         return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
     return np.concatenate(src), np.concatenate(dst), np.concatenate(score)
+
+
+def cluster_plan(labels, chunk_rows: int) -> Tuple[np.ndarray, np.ndarray, List[Tuple[int, int]]]:
+    """-> (order, end, chunks) for a cluster-scoped self-join.  order (n,) int64: the stable argsort of the labels, so a
+    cluster is a run of sorted positions holding ASCENDING row ids; end (n,) int64: the exclusive end, in sorted positions, of
+    the run that holds position i; chunks: [b0, b1) position ranges of whole runs with at most chunk_rows rows each (a longer
+    run is a chunk of its own), covering [0, n) in order.  labels: any integers (negative, not dense); host arrays."""
+    labels = np.asarray(labels).reshape(-1)
+    if labels.dtype.kind not in "iu":
+        raise ValueError(f"labels: expected integers, got {labels.dtype}")
+    chunk_rows = max(1, int(chunk_rows))
+    n = labels.size
+    key = labels
+    if n and int(labels.max()) - int(labels.min()) < 1 << 16:
+        key = (labels - labels.min()).astype(np.uint16)      # numpy sorts 16-bit keys by radix: 6 x faster at 2 M rows
+    order = np.argsort(key, kind="stable").astype(np.int64, copy=False)
+    sl = labels[order]
+    starts = np.flatnonzero(np.concatenate([[True], sl[1:] != sl[:-1]])) if n else np.zeros(0, np.int64)
+    ends = np.append(starts[1:], n)[: starts.size]
+    end = np.repeat(ends, ends - starts).astype(np.int64, copy=False)
+    chunks, b0 = [], 0
+    for a, b in zip(starts.tolist(), ends.tolist()):
+        if b - b0 > chunk_rows and a > b0:      # this run no longer fits: close the chunk before it
+            chunks.append((b0, a))
+            b0 = a
+    if n:
+        chunks.append((b0, n))
+    return order, end, chunks
+
+
+def _gather_rows(vectors, rows: np.ndarray, device) -> torch.Tensor:
+    """vectors[rows] on the device: a device tensor is indexed there; a host tensor, array or memmap on the host."""
+    if isinstance(vectors, torch.Tensor):
+        return vectors[torch.from_numpy(rows).to(vectors.device)].to(device)
+    return torch.from_numpy(np.ascontiguousarray(vectors[rows])).to(device)
+
+
+def clustered_duplicate_edges(vectors, labels, threshold: float, chunk_rows: int = 1 << 22,
+                              max_edges: int = DEFAULT_MAX_EDGES, device="cuda") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """-> (src int64, dst int64, score float32): `duplicate_edges` restricted to pairs with equal labels -- the same order
+    (src < dst, sorted by (src, dst)) and the same score bits.  vectors (n, d): a device tensor, a host array or a memmap
+    (rounded to bf16 as FlatIPIndex.add rounds); labels (n,): any integers.
+
+    Per chunk of cluster_plan(labels, chunk_rows) the rows are gathered in label order into an index of their own and ONE
+    windowed self-join (min_id = own position, end_id = the cluster's end) walks the block-diagonal band of the chunk; ids map
+    back through `order`.  Rows of a cluster keep ascending ids under the stable sort, so src < dst needs no swap.  More than
+    max_edges pairs raise ValueError before they are allocated."""
+    from .search import FlatIPIndex
+
+    n, d = int(np.shape(vectors)[0]), int(np.shape(vectors)[1])
+    if np.shape(labels) != (n,):
+        raise ValueError(f"labels has shape {tuple(np.shape(labels))} for {n} rows")
+    lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    order, end, chunks = cluster_plan(lab, chunk_rows)
+    src, dst, score = [], [], []
+    total = 0
+    for b0, b1 in chunks:
+        index = FlatIPIndex(d, device=device)
+        index.add(_gather_rows(vectors, order[b0:b1], index.device))
+        pos = torch.arange(b1 - b0, dtype=torch.int64, device=index.device)
+        try:
+            lims, s, ids = index.range_search(index.vectors, float(threshold), min_id=pos,
+                                              end_id=torch.from_numpy(end[b0:b1] - b0), max_results=max_edges - total)
+        except ValueError as e:
+            raise ValueError(f"clustered_duplicate_edges: more than max_edges = {max_edges} pairs above {threshold} "
+                             f"({total} before sorted rows {b0}:{b1}; {e})") from None
+        total += int(ids.numel())
+        if ids.numel():
+            src.append(order[b0 + torch.repeat_interleave(pos, lims[1:] - lims[:-1]).cpu().numpy()])
+            dst.append(order[b0 + ids.cpu().numpy()])
+            score.append(s.cpu().numpy())
+    if not src:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+    src, dst, score = np.concatenate(src), np.concatenate(dst), np.concatenate(score)
+    by = np.lexsort((dst, src))
+    return src[by], dst[by], score[by]
+
+
+def edge_recall(index, src, dst, threshold: float, sample: int = 4096, seed: int = 0) -> Tuple[int, int, float]:
+    """-> (found, exact, recall) of an edge list against the exact answer, on a seeded sample S of the stored rows (sample >= n:
+    all rows).  exact = sum over r in S of the number of rows n != r with s(r, n) > threshold -- two range_count calls,
+    min_id = r (the rows after r) and end_id = r (the rows before it); found = sum over r in S of r's degree in (src, dst);
+    recall = found / exact, 1.0 when exact == 0."""
+    n = index.ntotal
+    src, dst = _edges(n, src, dst)
+    rows = np.arange(n) if int(sample) >= n else np.sort(np.random.default_rng(seed).choice(n, int(sample), replace=False))
+    exact = 0
+    if rows.size:
+        r = torch.from_numpy(rows).to(index.device)
+        q = index.vectors[r]
+        exact = int(index.range_count(q, float(threshold), min_id=r).sum()) + \
+            int(index.range_count(q, float(threshold), end_id=r).sum())
+    degree = np.bincount(src, minlength=n) + np.bincount(dst, minlength=n)
+    found = int(degree[rows].sum())
+    return found, exact, (found / exact if exact else 1.0)
 
 
 def _edges(n: int, src, dst) -> Tuple[np.ndarray, np.ndarray]:

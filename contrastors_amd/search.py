@@ -66,6 +66,37 @@ def _exclusion_csr(exclude, M: int, device) -> Tuple[Optional[torch.Tensor], Opt
     return row_ptr.to(device), ids.to(device)
 
 
+TILE = 128                         # rows per query tile and ids per corpus tile of the search kernels
+
+
+def window_band(min_id, end_id, M: int, N: int) -> torch.Tensor:
+    """-> (ceil(M / 128),) int64, on the inputs' device: the corpus tiles t1 - t0 that each 128-row query tile of a windowed
+    range search walks (cx_range_window_count).  Over the tile's rows whose window min_id < n < end_id is not empty after
+    clamping min_id to [-1, N] and end_id to [0, N]:  t0 = (min min_id + 1) // 128,  t1 = ceil(max end_id / 128);  a tile
+    without such a row walks nothing.  min_id / end_id: (M,) int64 tensors or None (-1 / N everywhere).  Its prefix sum is the
+    kernel's band_ptr and its sum sizes the workspace."""
+    dev = (min_id if min_id is not None else end_id).device if (min_id is not None or end_id is not None) else "cpu"
+    mid = torch.full((M,), -1, dtype=torch.int64, device=dev) if min_id is None else min_id.clamp(-1, N)
+    end = torch.full((M,), N, dtype=torch.int64, device=dev) if end_id is None else end_id.clamp(0, N)
+    tiles_m = (M + TILE - 1) // TILE
+    live = end > mid + 1
+    pad = tiles_m * TILE - M
+    lo = torch.nn.functional.pad(torch.where(live, mid, N), (0, pad), value=N).view(tiles_m, TILE).amin(1)
+    hi = torch.nn.functional.pad(torch.where(live, end, 0), (0, pad), value=0).view(tiles_m, TILE).amax(1)
+    return torch.where(hi > 0, (hi + TILE - 1) // TILE - (lo + 1) // TILE, 0)
+
+
+def _window_ws_bytes(M: int, N: int, band_ptr: np.ndarray, mb: int, nsplit: int):
+    """cx_range_window_ws_bytes of every query batch of mb rows (mb == M or a multiple of 128)."""
+    h = _C.lib()
+    out = []
+    for b0 in range(0, M, mb):
+        m = min(mb, M - b0)
+        tiles = int(band_ptr[(b0 + m + TILE - 1) // TILE] - band_ptr[b0 // TILE])
+        out.append(h.cx_range_window_ws_bytes(m, N, tiles, nsplit))
+    return out
+
+
 class FlatIPIndex:
     """Exact maximum-inner-product index over bf16 vectors on one GPU (faiss IndexFlatIP with useFloat16)."""
 
@@ -239,8 +270,8 @@ class FlatIPIndex:
             m = max(128, (m // 2) // 128 * 128)
         return m
 
-    def _range_bounds(self, radius, min_id, M: int):
-        """radius (a scalar or M values) and min_id (None or M ids) -> device tensors (M,) float32 and (M,) int64 / None."""
+    def _range_bounds(self, radius, min_id, M: int, end_id=None):
+        """radius (a scalar or M values), min_id and end_id (None or M ids) -> device tensors (M,) float32 and (M,) int64 / None."""
         if isinstance(radius, (int, float)):
             rad = torch.full((M,), float(radius), dtype=torch.float32, device=self.device)
         else:
@@ -250,73 +281,104 @@ class FlatIPIndex:
                 rad = rad.expand(M).contiguous()
             if rad.numel() != M:
                 raise ValueError(f"radius has {rad.numel()} entries for {M} queries")
-        mid = None
-        if min_id is not None:
-            mid = torch.as_tensor(np.asarray(min_id) if not isinstance(min_id, torch.Tensor) else min_id)
-            if mid.dtype.is_floating_point or mid.dtype == torch.bool:
-                raise ValueError(f"min_id: expected integer ids, got {mid.dtype}")
-            mid = mid.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
-            if mid.numel() != M:
-                raise ValueError(f"min_id has {mid.numel()} entries for {M} queries")
-        return rad, mid
+        ids = []
+        for name, v in (("min_id", min_id), ("end_id", end_id)):
+            if v is not None:
+                v = torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v)
+                if v.dtype.is_floating_point or v.dtype == torch.bool:
+                    raise ValueError(f"{name}: expected integer ids, got {v.dtype}")
+                v = v.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+                if v.numel() != M:
+                    raise ValueError(f"{name} has {v.numel()} entries for {M} queries")
+            ids.append(v)
+        return rad, ids[0], ids[1]
 
-    def _range_batches(self, q, rad, mid, nsplit: int):
-        """Per query batch, after its cx_range_count: (b0, m, the C-ABI arguments shared with cx_range_emit (Q .. ws), counts
-        (m,) int64).  One workspace serves all batches: a batch's emit must be launched before the next batch is drawn."""
+    def range_window_batch_rows(self, M: int, band_ptr: np.ndarray, nsplit: int = 0) -> int:
+        """The largest query batch (all of M, else halved down to a multiple of 128) whose cx_range_window_ws_bytes fits the
+        bound in every batch.  band_ptr: the host prefix sum (tiles_m + 1) of window_band over all M rows."""
+        m = M
+        while m > 128 and max(_window_ws_bytes(M, self.ntotal, band_ptr, m, nsplit)) > self.workspace_bytes:
+            m = max(128, (m // 2) // 128 * 128)
+        return m
+
+    def _range_batches(self, q, rad, mid, nsplit: int, end=None):
+        """Per query batch, after its count pass: (b0, m, the emit entry point, the C-ABI arguments it shares with the count
+        pass (Q .. ws), counts (m,) int64).  One workspace serves all batches: a batch's emit must be launched before the next
+        batch is drawn.  end is None: cx_range_count / cx_range_emit; otherwise the windowed pair, whose band description and
+        workspace size both come from window_band(mid, end)."""
         h = _C.lib()
         M = q.shape[0]
-        mb = self.range_batch_rows(M, nsplit)
-        last = M - (M - 1) // mb * mb
-        nbytes = max(h.cx_range_ws_bytes(mb, self.ntotal, nsplit), h.cx_range_ws_bytes(last, self.ntotal, nsplit))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         D = self.vectors
         stream = _C.cur_stream()
+        if end is None:
+            mb = self.range_batch_rows(M, nsplit)
+            last = M - (M - 1) // mb * mb
+            nbytes = max(h.cx_range_ws_bytes(mb, self.ntotal, nsplit), h.cx_range_ws_bytes(last, self.ntotal, nsplit))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            for b0 in range(0, M, mb):
+                m = min(mb, M - b0)
+                args = (q[b0].data_ptr(), D.data_ptr(), m, self.ntotal, self.d, self.d, self.d, rad[b0:].data_ptr(),
+                        None if mid is None else mid[b0:].data_ptr(), int(nsplit), ws.data_ptr())
+                counts = torch.empty(m, dtype=torch.int64, device=self.device)
+                _C.check(h.cx_range_count(*args, counts.data_ptr(), stream), "cx_range_count")
+                yield b0, m, h.cx_range_emit, args, counts
+            return
+        band_ptr = np.zeros((M + TILE - 1) // TILE + 1, dtype=np.int64)
+        np.cumsum(window_band(mid, end, M, self.ntotal).cpu().numpy(), out=band_ptr[1:])   # (the host waits for the band here)
+        mb = self.range_window_batch_rows(M, band_ptr, nsplit)
+        ws = torch.empty(max(_window_ws_bytes(M, self.ntotal, band_ptr, mb, nsplit)), dtype=torch.uint8, device=self.device)
         for b0 in range(0, M, mb):
             m = min(mb, M - b0)
+            t0, t1 = b0 // TILE, (b0 + m + TILE - 1) // TILE
+            bp = torch.from_numpy(band_ptr[t0: t1 + 1] - band_ptr[t0]).to(self.device)
             args = (q[b0].data_ptr(), D.data_ptr(), m, self.ntotal, self.d, self.d, self.d, rad[b0:].data_ptr(),
-                    None if mid is None else mid[b0:].data_ptr(), int(nsplit), ws.data_ptr())
+                    None if mid is None else mid[b0:].data_ptr(), end[b0:].data_ptr(), bp.data_ptr(),
+                    int(band_ptr[t1] - band_ptr[t0]), int(nsplit), ws.data_ptr())
             counts = torch.empty(m, dtype=torch.int64, device=self.device)
-            _C.check(h.cx_range_count(*args, counts.data_ptr(), stream), "cx_range_count")
-            yield b0, m, args, counts
+            _C.check(h.cx_range_window_count(*args, counts.data_ptr(), stream), "cx_range_window_count")
+            yield b0, m, h.cx_range_window_emit, args, counts   # (bp lives in this frame until the batch's emit is launched)
 
-    def range_count(self, queries, radius, min_id=None, nsplit: int = 0):
-        """-> counts (M,) int64: per query the number of stored vectors n with score > radius (strict) and n > min_id
-        (cx_range_count, csrc/range.hip; the (M, ntotal) scores are never written).  radius: a scalar or M values (NaN admits
-        nothing, -inf every finite score); min_id: None (= -1) or M ids.  numpy in -> numpy out, torch in -> torch out on
-        the index's device.  nsplit has no effect on the result."""
+    def range_count(self, queries, radius, min_id=None, end_id=None, nsplit: int = 0):
+        """-> counts (M,) int64: per query the number of stored vectors n with score > radius (strict) and min_id < n < end_id
+        (cx_range_count, or cx_range_window_count when end_id is given; csrc/range.hip; the (M, ntotal) scores are never
+        written).  radius: a scalar or M values (NaN admits nothing, -inf every finite score); min_id: None (= -1) or M ids;
+        end_id: None (= ntotal) or M ids.  numpy in -> numpy out, torch in -> torch out on the index's device.  nsplit has no
+        effect on the result."""
         as_numpy = not isinstance(queries, torch.Tensor)
         q = _to_device_2d(queries, self.d, self.device)
         M = q.shape[0]
-        rad, mid = self._range_bounds(radius, min_id, M)
+        rad, mid, end = self._range_bounds(radius, min_id, M, end_id)
         counts = torch.zeros(M, dtype=torch.int64, device=self.device)
         if M and self.ntotal:
             with torch.cuda.device(self.device):
-                for b0, m, _, c in self._range_batches(q, rad, mid, nsplit):
+                for b0, m, _, _, c in self._range_batches(q, rad, mid, nsplit, end):
                     counts[b0: b0 + m] = c
         return counts.cpu().numpy() if as_numpy else counts
 
-    def range_search(self, queries, radius, min_id=None, max_results: int = 1 << 27, nsplit: int = 0):
+    def range_search(self, queries, radius, min_id=None, end_id=None, max_results: int = 1 << 27, nsplit: int = 0):
         """-> (lims (M + 1) int64, scores (nnz) float32, ids (nnz) int64), faiss's range_search layout: the stored vectors
-        with score > radius[m] (strict) and id > min_id[m] of query m are entries lims[m] : lims[m + 1], in ascending id
-        order, with the score bits search() gives the pair.  However many there are: nothing is cut at a k.
+        with score > radius[m] (strict) and min_id[m] < id < end_id[m] of query m are entries lims[m] : lims[m + 1], in
+        ascending id order, with the score bits search() gives the pair.  However many there are: nothing is cut at a k.
 
         Per query batch the kernel counts first (cx_range_count); the total is read on the host and a running total above
         max_results raises ValueError BEFORE the batch's results are allocated; only then cx_range_emit writes them (not
-        launched for a batch without results).  radius, min_id, nsplit: as range_count.  min_id = the queries' own corpus
-        ids turns a self-join into every unordered pair once.  numpy in -> numpy out, torch in -> torch out."""
+        launched for a batch without results).  radius, min_id, end_id, nsplit: as range_count.  min_id = the queries' own
+        corpus ids turns a self-join into every unordered pair once; with end_id (the windowed kernels) only the corpus tiles
+        between a query tile's smallest min_id and largest end_id are computed, so rows sorted by a partition with
+        end_id = the end of the row's part join every part with itself in one call (contrastors_amd.dedup).  numpy in ->
+        numpy out, torch in -> torch out."""
         as_numpy = not isinstance(queries, torch.Tensor)
         q = _to_device_2d(queries, self.d, self.device)
         M = q.shape[0]
-        rad, mid = self._range_bounds(radius, min_id, M)
+        rad, mid, end = self._range_bounds(radius, min_id, M, end_id)
         max_results = int(max_results)
         lims = torch.zeros(M + 1, dtype=torch.int64, device=self.device)
         out_s, out_i = [], []
         total = 0
         if M and self.ntotal:
-            h = _C.lib()
             with torch.cuda.device(self.device):
                 stream = _C.cur_stream()
-                for b0, m, args, counts in self._range_batches(q, rad, mid, nsplit):
+                for b0, m, emit, args, counts in self._range_batches(q, rad, mid, nsplit, end):
                     blims = torch.zeros(m + 1, dtype=torch.int64, device=self.device)
                     torch.cumsum(counts, 0, out=blims[1:])
                     n = int(blims[-1])   # (the host waits for the count pass here)
@@ -329,7 +391,7 @@ class FlatIPIndex:
                         continue
                     s = torch.empty(n, dtype=torch.float32, device=self.device)
                     i = torch.empty(n, dtype=torch.int64, device=self.device)
-                    _C.check(h.cx_range_emit(*args, blims.data_ptr(), s.data_ptr(), i.data_ptr(), stream), "cx_range_emit")
+                    _C.check(emit(*args, blims.data_ptr(), s.data_ptr(), i.data_ptr(), stream), "cx_range_emit")
                     out_s.append(s)
                     out_i.append(i)
         if len(out_s) == 1:

@@ -402,6 +402,28 @@ int cx_range_count(const uint16_t* Q, const uint16_t* D, int M, long N, int d, l
 int cx_range_emit(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const float* radius,
                   const int64_t* min_id, int nsplit, const void* ws, const int64_t* lims, float* out_scores, int64_t* out_ids,
                   void* stream);
+/* The same search with a WINDOW of ids per row (cluster-scoped near-duplicate search over label-sorted rows: min_id = the row's
+ * own position, end_id = its cluster's end; any partition; "neighbours before row r").  Additive: cx_abi_version stays 10.
+ * end_id:(M) int64 device memory or NULL (= N everywhere), clamped to [0, N].  Row m admits n iff s(m,n) > radius[m] (strict)
+ * and min_id[m] < n < end_id[m]; a NaN radius admits nothing, -inf every id of the window, a window with
+ * end_id <= min_id + 1 nothing.  Operands, alignment rules, error codes, the two-pass contract, the output layout (ascending
+ * ids per row, unflagged tiles skipped) and the independence of nsplit / batching / scheduling are those of cx_range_count /
+ * cx_range_emit; deterministic, no global atomics.
+ * The band: query tile tm (rows 128 tm ..) walks corpus tiles [t0, t1) only, t0 = (min min_id + 1) / 128 and
+ * t1 = ceil(max end_id / 128) over its rows with a non-empty window (no such row: nothing).  The workspace holds one flag word
+ * per band tile: band_ptr:(ceil(M / 128) + 1) int64 DEVICE memory = the exclusive prefix sum of t1 - t0, band_tiles = its last
+ * entry, read by the caller.  A walk is cut to band_ptr[tm + 1] - band_ptr[tm] tiles and band_ptr is clamped to
+ * [0, band_tiles]: arrays inconsistent with each other give wrong results, never an access outside ws.
+ * nsplit divides a query tile's band (<= 0: chosen from the query tiles and the mean band; thousands of query tiles: 1).
+ * ws: 16-B aligned, cx_range_window_ws_bytes(M, N, band_tiles, nsplit) bytes -- partial counts + 4 bytes per band tile,
+ * nothing proportional to tiles_m x tiles_n -- need not be initialised.  A NULL band_ptr or band_tiles < 0: CX_ERR_ARG. */
+long cx_range_window_ws_bytes(int M, long N, long band_tiles, int nsplit);
+int cx_range_window_count(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const float* radius,
+                          const int64_t* min_id, const int64_t* end_id, const int64_t* band_ptr, long band_tiles, int nsplit,
+                          void* ws, int64_t* counts, void* stream);
+int cx_range_window_emit(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, const float* radius,
+                         const int64_t* min_id, const int64_t* end_id, const int64_t* band_ptr, long band_tiles, int nsplit,
+                         const void* ws, const int64_t* lims, float* out_scores, int64_t* out_ids, void* stream);
 /* ---- k-means over bf16 points: fused assignment and a deterministic centroid update (cluster-scoped curation, clustering
  *          evaluation, coarse quantisers; csrc/kmeans.hip).  Additive: cx_abi_version stays 10. ------------------------------
  * cx_kmeans_assign: X:(N,d) ldx points, C:(K,d) ldc centroids (alignment rules and d as cx_search_topk; N, K <= 2^31 - 129,
