@@ -184,6 +184,9 @@ _SIGS = {
     "cx_infonce_bwd": (i32, [vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "cx_search_ws_bytes": (i64, [i32, i64, i32, i32]),
     "cx_search_topk": (i32, [vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "cx_search_window_ws_bytes": (i64, [i32, i32]),
+    "cx_search_window_topk": (i32, [vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "cx_topk_merge_lists": (i32, [vp, vp, i64, i32, vp, i32, i32, vp, i64, vp, vp, vp]),
     "cx_rank_ws_bytes": (i64, [i32, i64, i64, i32]),
     "cx_rank_targets": (i32, [vp, vp, i32, i64, i32, i64, i64, vp, vp, i32, vp, vp, vp, vp]),
     "cx_range_ws_bytes": (i64, [i32, i64, i32]),

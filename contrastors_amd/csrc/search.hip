@@ -14,6 +14,15 @@
 // Order: descending score, ties to the lower id -- a strict total order on (score, id).  Every score has ONE instruction
 // sequence (the same K order whatever tile or split it falls in), so the result is the unique top-k of that order and is
 // bit-identical for any split count.  Rows with fewer than k admissible documents are padded with (-inf, -1).
+//
+// cx_search_window_topk is stage 1 instantiated with WIN = true: row m also has an id window min_id[m] < n < end_id[m]
+// (range.hip's convention), kept in LDS next to thr / bel and tested wherever a column is tested against N.  A query tile walks
+// the corpus tiles [t0, t1) only -- t0 from the smallest min_id and t1 from the largest end_id among its rows with a non-empty
+// window -- in one piece (nsplit = 1: the band is short, and ids still grow along the walk).  What an IVF index needs: rows
+// sorted by list, (query, probed list) pairs sorted by list, so that a 128-pair tile walks a short run of consecutive lists.
+// cx_topk_merge_lists is stage 2 behind an indirection: the lists of an output row are named by src and live in (P, k) score /
+// id arrays as the search entry points write them; ids may be mapped on the way out (list positions -> original ids).
+#include <type_traits>
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
 
@@ -52,6 +61,8 @@ struct SearchParams {
     const int64_t* xptr;   // (M + 1) CSR row pointers into xids (absolute), or null
     const int64_t* xids;
     const float* below;    // (M) exclusive upper bound on the score, or null
+    const int64_t* min_id; // WIN: (M) exclusive lower id bound, or null (= -1 everywhere)
+    const int64_t* end_id; // WIN: (M) exclusive upper id bound, or null (= N everywhere)
     Cand* lists;           // (M, nsplit, k)
     int* counts;           // (M, nsplit)
 };
@@ -94,9 +105,17 @@ struct SearchLds {
     int any;
 };
 
+struct WinSearchLds : SearchLds {
+    int mid[TM], end[TM];         // min_id clamped to [-1, N], end_id clamped to [0, N]
+    int minmid, maxend;           // over the tile's rows with a non-empty window
+};
+
+template <bool WIN> using SearchLdsT = typename std::conditional<WIN, WinSearchLds, SearchLds>::type;
+
 // one wave: insert the admissible scores of tile row `row` (scores in `tile`) into the row's running list
-CX_DEVICE void insert_row(const SearchParams& p, SearchLds& L, const float* tile, int row, int m, int n0, int split, int wave,
-                          int lane) {
+template <bool WIN>
+CX_DEVICE void insert_row(const SearchParams& p, SearchLdsT<WIN>& L, const float* tile, int row, int m, int n0, int split,
+                          int wave, int lane) {
     const float thr = L.thr[row], bel = L.bel[row];
     const int cnt = L.cnt[row];
     const int64_t x0 = p.xptr ? p.xptr[m] : 0, x1 = p.xptr ? p.xptr[m + 1] : 0;
@@ -109,6 +128,7 @@ CX_DEVICE void insert_row(const SearchParams& p, SearchLds& L, const float* tile
         const int j = lane + 64 * h, n = n0 + j;
         const float s = tile[row * TN + j];
         bool ok = n < p.N && s > thr && s < bel;
+        if constexpr (WIN) ok = ok && n > L.mid[row] && n < L.end[row];
         if (ok)
             for (int64_t e = x0; e < x1; ++e)
                 if (p.xids[e] == n) ok = false;
@@ -148,26 +168,52 @@ CX_DEVICE void insert_row(const SearchParams& p, SearchLds& L, const float* tile
     wave_sync();
 }
 
-__global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
+template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
-    SearchLds& L = *reinterpret_cast<SearchLds*>(dsm);
+    SearchLdsT<WIN>& L = *reinterpret_cast<SearchLdsT<WIN>*>(dsm);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
     const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
     const int m0 = tm * TM;
-    const int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
+    int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
     const int nk = p.d / BK;
 
+    if constexpr (WIN) {
+        if (tid == 0) { L.minmid = 0x7fffffff; L.maxend = 0; }
+        __syncthreads();
+    }
     if (tid < TM) {
         const int m = m0 + tid;
         // rows past M never pass the threshold test
-        L.thr[tid] = m < p.M ? -INFINITY : INFINITY;
+        bool live = m < p.M;
+        if constexpr (WIN) {
+            int id = -1, e = 0;
+            if (live) {
+                const int64_t v = p.min_id ? p.min_id[m] : (int64_t)-1;
+                const int64_t w = p.end_id ? p.end_id[m] : (int64_t)p.N;
+                id = (int)min(max(v, (int64_t)-1), (int64_t)p.N);
+                e = (int)min(max(w, (int64_t)0), (int64_t)p.N);
+                live = e > id + 1;   // ... nor do rows with an empty window, which stay out of the walk's bounds
+                if (live) {
+                    atomicMin(&L.minmid, id);   // (LDS)
+                    atomicMax(&L.maxend, e);
+                }
+            }
+            L.mid[tid] = id;
+            L.end[tid] = e;
+        }
+        L.thr[tid] = live ? -INFINITY : INFINITY;
         L.bel[tid] = (m < p.M && p.below) ? p.below[m] : INFINITY;
         L.cnt[tid] = 0;
         L.flag[tid] = 0;
     }
     if (tid == 0) L.any = 0;
     __syncthreads();
+    if constexpr (WIN) {
+        // a non-empty row has mid + 1 < end <= N: t_begin < t_end <= tiles_n; a tile of empty windows walks nothing
+        t_begin = L.maxend > 0 ? (L.minmid + 1) / TN : 0;
+        t_end = L.maxend > 0 ? (L.maxend + TN - 1) / TN : 0;
+    }
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * TN;
@@ -211,13 +257,25 @@ __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
             const int row = wq * 64 + a * 16 + l15;
             const float thr = L.thr[row], bel = L.bel[row];
             bool h = false;
+            if constexpr (WIN) {
+                const int nb = n0 + wd * 64 + 4 * lh;
+                const int lim = L.mid[row] - nb, top = L.end[row] - nb;   // column nb + c is inside the window  <=>  lim < c < top
 #pragma unroll
-            for (int b = 0; b < 4; ++b)
+                for (int b = 0; b < 4; ++b)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = acc[a][b][r];
-                    h |= (v > thr) & (v < bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
-                }
+                    for (int r = 0; r < 4; ++r) {
+                        const float v = acc[a][b][r];
+                        h |= (v > thr) & (v < bel) & (b * 16 + r > lim) & (b * 16 + r < top);   // (end <= N)
+                    }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float v = acc[a][b][r];
+                        h |= (v > thr) & (v < bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
+                    }
+            }
             if (h) L.flag[row] = 1;
             hit |= h;
         }
@@ -232,7 +290,7 @@ __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
                     *reinterpret_cast<f32x4_t*>(tile + (wq * 64 + a * 16 + l15) * TN + wd * 64 + b * 16 + 4 * lh) = acc[a][b];
             __syncthreads();
             for (int row = wave; row < TM; row += 4)
-                if (L.flag[row]) insert_row(p, L, tile, row, m0 + row, n0, split, wave, lane);
+                if (L.flag[row]) insert_row<WIN>(p, L, tile, row, m0 + row, n0, split, wave, lane);
             __syncthreads();
             if (tid < TM) L.flag[tid] = 0;
             if (tid == 0) L.any = 0;
@@ -242,24 +300,93 @@ __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
     if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
 }
 
-// one wave per query row: merge the row's nsplit sorted lists into its top-k
-__global__ __launch_bounds__(256) void merge_splits_kernel(const Cand* __restrict__ lists, const int* __restrict__ counts,
-                                                           int M, int nsplit, int k, float* __restrict__ out_s,
-                                                           int64_t* __restrict__ out_id) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const Cand* base = lists + (int64_t)row * nsplit * k;
-    const int* cnt = counts + (int64_t)row * nsplit;
+constexpr int MAXLISTS = 256;       // lists merged into one output row (>= MAXSPLIT)
+
+// What the merge orders: (score, reported id).  int64 ids: the reported id of cx_topk_merge_lists is any int64 of id_map.
+struct Ent {
+    float s;
+    int64_t id;
+};
+
+// cx_search_topk's workspace: output row m merges the lists m * nsplit + [0, nsplit); a list's length is in counts
+struct SplitLists {
+    const Cand* lists;
+    const int* counts;
+    int nsplit, k;
+    CX_DEVICE int64_t list_of(int row, int l) const { return (int64_t)row * nsplit + l; }
+    CX_DEVICE int count(int64_t r) const { return counts[r]; }
+    CX_DEVICE float score(int64_t r, int j) const { return lists[r * k + j].s; }
+    CX_DEVICE int64_t id(int64_t r, int j) const { return lists[r * k + j].id; }
+};
+
+// (P, k) score / id arrays as the search entry points write them: sorted rows padded with (-inf, -1), so a list ends at its
+// first negative id.  Output row m merges the lists src[m][0 .. L); an entry outside [0, P) names no list.  id_map (or null):
+// the reported id of position n is id_map[n], n clamped to [0, N) for the read.
+struct PaddedLists {
+    const float* s;
+    const int64_t* ids;
+    const int64_t* src;
+    const int64_t* id_map;
+    int64_t P, N;
+    int L, k;
+    CX_DEVICE int64_t list_of(int row, int l) const {
+        const int64_t r = src[(int64_t)row * L + l];
+        return (r >= 0 && r < P) ? r : -1;
+    }
+    CX_DEVICE int count(int64_t r) const {
+        int lo = 0, hi = k;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ids[r * k + mid] >= 0) lo = mid + 1; else hi = mid;
+        }
+        return lo;
+    }
+    CX_DEVICE float score(int64_t r, int j) const { return s[r * k + j]; }
+    CX_DEVICE int64_t id(int64_t r, int j) const {
+        const int64_t n = ids[r * k + j];
+        return id_map ? id_map[min(max(n, (int64_t)0), N - 1)] : n;
+    }
+};
+
+// number of entries of the sorted list r (n entries) that beat e; an id is read only where the scores tie
+template <class Lists> CX_DEVICE int count_beating(const Lists& S, int64_t r, int n, Ent e) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float s = S.score(r, mid);
+        const bool b = s != e.s ? s > e.s : S.id(r, mid) < e.id;
+        if (b) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// one wave per output row: merge the row's L sorted, disjoint lists into its top-k by (score descending, reported id
+// ascending).  Every list must be sorted in that order (a list whose reported ids ascend with its positions is).
+template <class Lists>
+__global__ __launch_bounds__(256) void merge_lists_kernel(Lists S, int M, int L, int k, float* __restrict__ out_s,
+                                                          int64_t* __restrict__ out_id) {
+    __shared__ int64_t lrow_[4][MAXLISTS];
+    __shared__ int lcnt_[4][MAXLISTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= M) return;   // (no workgroup barrier below)
+    int64_t* lrow = lrow_[wave];
+    int* cnt = lcnt_[wave];
+    for (int l = lane; l < L; l += 64) {
+        const int64_t r = S.list_of(row, l);
+        lrow[l] = r;
+        cnt[l] = r < 0 ? 0 : min(S.count(r), k);
+    }
+    wave_sync();
     int total = 0;
-    for (int s = 0; s < nsplit; ++s) total += cnt[s];
-    for (int idx = lane; idx < nsplit * k; idx += 64) {
+    for (int s = 0; s < L; ++s) total += cnt[s];
+    for (int idx = lane; idx < L * k; idx += 64) {
         const int s = idx / k, j = idx - s * k;
         if (j >= cnt[s]) continue;
-        const Cand e = base[(int64_t)s * k + j];
+        const Ent e = Ent{S.score(lrow[s], j), S.id(lrow[s], j)};
         int rank = j;
-        for (int s2 = 0; s2 < nsplit && rank < k; ++s2)
-            if (s2 != s) rank += count_beating(base + (int64_t)s2 * k, cnt[s2], e);
+        for (int s2 = 0; s2 < L && rank < k; ++s2)
+            if (s2 != s && cnt[s2] > 0) rank += count_beating(S, lrow[s2], cnt[s2], e);
         if (rank < k) {
             out_s[(int64_t)row * k + rank] = e.s;
             out_id[(int64_t)row * k + rank] = e.id;
@@ -312,12 +439,62 @@ int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, l
         p.lists = lists; p.counts = counts;
         const int tiles_m = (M + TM - 1) / TM;
         static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel), (int)sizeof(SearchLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(SearchLds), s, p);
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel<false>), (int)sizeof(SearchLds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_tiles_kernel<false>, dim3(tiles_m * ns), dim3(256), sizeof(SearchLds), s, p);
         if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
     }
     // N == 0: counts stays null and every row is padding
-    hipLaunchKernelGGL(merge_splits_kernel, dim3((M + 3) / 4), dim3(256), 0, s, lists, counts, M, N > 0 ? ns : 0, k,
+    const SplitLists S = {lists, counts, ns, k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_search_window_ws_bytes(int M, int k) {
+    if (M <= 0 || k <= 0) return 0;
+    return (long)M * ((long)k * (long)sizeof(Cand) + (long)sizeof(int)) + 16;
+}
+
+int cx_search_window_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
+                          const int64_t* min_id, const int64_t* end_id, const int64_t* excl_ptr, const int64_t* excl_ids,
+                          const float* below, void* ws, float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Q || !out_scores || !out_ids || (N > 0 && (!D || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
+    if (ldq < d || (ldq % 8) != 0 || (N > 0 && (ldd < d || (ldd % 8) != 0))) return CX_ERR_ALIGN;
+    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    Cand* lists = reinterpret_cast<Cand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
+    if (N > 0) {
+        SearchParams p = {};
+        p.Q = Q; p.D = D; p.ldq = ldq; p.ldd = ldd;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = 1;   // one workgroup walks a query tile's whole band
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = p.tiles_n;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
+        p.min_id = min_id; p.end_id = end_id;
+        p.lists = lists; p.counts = counts;
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel<true>), (int)sizeof(WinSearchLds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_tiles_kernel<true>, dim3((M + TM - 1) / TM), dim3(256), sizeof(WinSearchLds), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    // the row's one list, padded, in the output layout
+    const SplitLists S = {lists, counts, 1, k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? 1 : 0, k, out_scores,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+int cx_topk_merge_lists(const float* scores, const int64_t* ids, long P, int k, const int64_t* src, int M, int L,
+                        const int64_t* id_map, long N, float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || P < 0 || k < 1 || k > MAXK || L < 1 || L > MAXLISTS || (id_map && N < 1)) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!src || !out_scores || !out_ids || (P > 0 && (!scores || !ids))) return CX_ERR_ARG;
+    const PaddedLists S = {scores, ids, src, id_map, (int64_t)P, (int64_t)N, L, k};
+    hipLaunchKernelGGL(merge_lists_kernel<PaddedLists>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, M, L, k,
                        out_scores, out_ids);
     return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
 }

@@ -51,6 +51,15 @@ def duplicate_edges(index, threshold: float, batch_rows: int = DEFAULT_BATCH_ROW
     return np.concatenate(src), np.concatenate(dst), np.concatenate(score)
 
 
+def label_order(labels: np.ndarray) -> np.ndarray:
+    """-> (n,) int64: the stable argsort of a 1-d integer host array, so equal labels keep ascending row ids (the sort of
+    cluster_plan and of IVFFlatIndex's lists)."""
+    key = labels
+    if labels.size and int(labels.max()) - int(labels.min()) < 1 << 16:
+        key = (labels - labels.min()).astype(np.uint16)      # numpy sorts 16-bit keys by radix: 6 x faster at 2 M rows
+    return np.argsort(key, kind="stable").astype(np.int64, copy=False)
+
+
 def cluster_plan(labels, chunk_rows: int) -> Tuple[np.ndarray, np.ndarray, List[Tuple[int, int]]]:
     """-> (order, end, chunks) for a cluster-scoped self-join.  order (n,) int64: the stable argsort of the labels, so a
     cluster is a run of sorted positions holding ASCENDING row ids; end (n,) int64: the exclusive end, in sorted positions, of
@@ -61,10 +70,7 @@ def cluster_plan(labels, chunk_rows: int) -> Tuple[np.ndarray, np.ndarray, List[
         raise ValueError(f"labels: expected integers, got {labels.dtype}")
     chunk_rows = max(1, int(chunk_rows))
     n = labels.size
-    key = labels
-    if n and int(labels.max()) - int(labels.min()) < 1 << 16:
-        key = (labels - labels.min()).astype(np.uint16)      # numpy sorts 16-bit keys by radix: 6 x faster at 2 M rows
-    order = np.argsort(key, kind="stable").astype(np.int64, copy=False)
+    order = label_order(labels)
     sl = labels[order]
     starts = np.flatnonzero(np.concatenate([[True], sl[1:] != sl[:-1]])) if n else np.zeros(0, np.int64)
     ends = np.append(starts[1:], n)[: starts.size]

@@ -9,6 +9,10 @@ positives) and a per-row exclusive score bound (margin * s(q, pos)).  `rank` giv
 `range_search`, which faiss has on the CPU only (csrc/range.hip; near-duplicate removal and decontamination on top of it are
 in contrastors_amd/dedup.py).
 
+`IVFFlatIndex` searches inside k-means lists instead of the whole corpus (faiss `IndexIVFFlat`): rows sorted by list, one
+windowed top-k launch over the (query, probed list) pairs sorted by list, one merge per query (csrc/search.hip,
+cx_search_window_topk / cx_topk_merge_lists); with every list probed it is `FlatIPIndex.search` bit for bit.
+
 `BinaryFlatIndex` is the same surface over sign codes (faiss `IndexBinaryFlat`, d / 8 bytes per vector) for the recipes
 trained with `hamming: true`; `rescore` / `search_binary_rescored` re-score its candidates exactly against the bf16 rows,
 which may stay on the host or in a memory-mapped file (csrc/search_binary.hip).
@@ -404,6 +408,256 @@ class FlatIPIndex:
         if as_numpy:
             return lims.cpu().numpy(), scores.cpu().numpy(), ids.cpu().numpy()
         return lims, scores, ids
+
+
+MAX_NPROBE = 256                 # cx_topk_merge_lists' bound on the lists merged into one row
+
+
+def ivf_pair_plan(probes: torch.Tensor, list_ptr: torch.Tensor):
+    """The work list of an IVF search, from torch ops on the inputs' device (CPU tensors too), no host synchronisation.
+
+    probes (M, L) int64: the lists each query probes (in any order; an entry outside [0, nlist) probes nothing);
+    list_ptr (nlist + 1) int64: list l holds the sorted-corpus positions list_ptr[l] : list_ptr[l + 1].  The M * L
+    (query, list) pairs are stable-sorted by list, so pair rows that share a list are adjacent (in ascending query order) and a
+    128-row tile of them spans a short run of consecutive lists.  -> (pair_query (P,), min_id (P,), end_id (P,), src (M, L)),
+    int64: pair row r searches query pair_query[r] inside the window min_id[r] < n < end_id[r] = its list, and src[m, j] is
+    the pair row of (query m, its j-th probe) -- the lists cx_topk_merge_lists merges into output row m."""
+    if probes.dim() != 2 or list_ptr.dim() != 1 or list_ptr.numel() < 1:
+        raise ValueError(f"expected probes (M, L) and list_ptr (nlist + 1), got {tuple(probes.shape)} and {tuple(list_ptr.shape)}")
+    M, L = probes.shape
+    nlist = list_ptr.numel() - 1
+    lists = probes.reshape(-1).to(torch.int64)
+    lp = list_ptr.to(torch.int64)
+    perm = torch.sort(lists, stable=True).indices
+    sl = lists[perm]
+    ok = (sl >= 0) & (sl < nlist)
+    sl = sl.clamp(0, max(nlist - 1, 0))
+    zero = torch.zeros_like(sl)
+    min_id = torch.where(ok, lp[sl] - 1, zero) if nlist else zero      # (0, 0): an empty window
+    end_id = torch.where(ok, lp[sl + 1], zero) if nlist else zero
+    src = torch.empty(M * L, dtype=torch.int64, device=probes.device)
+    src[perm] = torch.arange(M * L, dtype=torch.int64, device=probes.device)
+    return torch.div(perm, max(L, 1), rounding_mode="floor"), min_id, end_id, src.view(M, L)
+
+
+def ivf_pair_exclusions(row_ptr: torch.Tensor, ids: torch.Tensor, pair_query: torch.Tensor, inv_order: torch.Tensor,
+                        nprobe: int):
+    """The exclusion lists of the queries (CSR row_ptr (M + 1) from 0, ids: ORIGINAL corpus ids) as a CSR over the pair rows of
+    ivf_pair_plan, in sorted-corpus POSITIONS: pair row r gets the list of query pair_query[r], every id through inv_order
+    (inv_order[order[p]] = p); ids outside [0, N) become -1, which no position equals.  Every query has nprobe pair rows, so
+    the result has nprobe * len(ids) entries -- known on the host, nothing is read back.  -> (pair_ptr (P + 1), pair_ids)."""
+    P, N = pair_query.numel(), inv_order.numel()
+    dev = pair_query.device
+    total = int(nprobe) * ids.numel()
+    plen = (row_ptr[1:] - row_ptr[:-1])[pair_query]
+    pair_ptr = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(plen, 0, out=pair_ptr[1:])
+    row = torch.repeat_interleave(torch.arange(P, dtype=torch.int64, device=dev), plen, output_size=total)
+    e = row_ptr[pair_query[row]] + (torch.arange(total, dtype=torch.int64, device=dev) - pair_ptr[row])
+    x = ids[e]
+    ok = (x >= 0) & (x < N)
+    pos = inv_order[x.clamp(0, max(N - 1, 0))] if N else x
+    return pair_ptr, torch.where(ok, pos, torch.full_like(x, -1))
+
+
+class IVFFlatIndex:
+    """Inverted-file index with uncompressed bf16 rows on one GPU (faiss IndexIVFFlat, inner product): a coarse quantiser of
+    nlist centroids, every stored row in the list of its best centroid, and a search that scores only the rows of the nprobe
+    lists whose centroids are nearest to the query.  Scores have the bits FlatIPIndex.search gives the pair, so probing every
+    list returns exactly its result.
+
+    The rows are kept sorted by list (a stable sort: a list is a run of ascending original ids); a search sorts its
+    (query, probed list) pairs by list too and ONE windowed top-k launch per batch (cx_search_window_topk) walks, for every
+    128-pair tile, only the corpus tiles of the lists that tile probes; cx_topk_merge_lists merges each query's nprobe lists
+    and maps positions back to original ids.  No per-list launches; nothing but sizes is read back.
+
+    The sort happens at the first search after an add and needs, at its peak, twice the corpus in device memory (the old
+    rows and their gathered copy).  Not here: L2, residual / PQ codes, host rows, save / load (centroids go in and out as
+    arrays), incremental adds without a re-sort."""
+
+    def __init__(self, d: int, nlist: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
+        if d % 64 or not 64 <= d <= 1024:
+            raise ValueError(f"d must be a multiple of 64 in [64, 1024], got {d}")
+        if not 1 <= int(nlist) <= MAX_NTOTAL:
+            raise ValueError(f"nlist must be in [1, {MAX_NTOTAL}], got {nlist}")
+        self.d, self.nlist = int(d), int(nlist)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("IVFFlatIndex runs on the GPU (cx_search_window_topk); there is no CPU path")
+        self.workspace_bytes = int(workspace_bytes)
+        self.seed = int(seed)
+        self._centroids: Optional[torch.Tensor] = None    # (nlist, d) fp32
+        self._coarse: Optional[FlatIPIndex] = None         # over the centroids' bf16 shadows
+        self.reset()
+
+    def reset(self) -> None:
+        """Drop the stored rows; the centroids stay."""
+        self._rows: Optional[torch.Tensor] = None         # (n sorted, d) bf16 in list order
+        self._order: Optional[torch.Tensor] = None        # (n sorted) int64: original id of every sorted position
+        self._inv: Optional[torch.Tensor] = None          # (n sorted) int64: its inverse
+        self._labels: Optional[torch.Tensor] = None       # (n sorted) int32, ascending
+        self._list_ptr: Optional[torch.Tensor] = None     # (nlist + 1) int64
+        self._pending = []                                # (rows, labels) chunks added since the last sort
+        self.ntotal = 0
+
+    @property
+    def is_trained(self) -> bool:
+        return self._centroids is not None
+
+    @property
+    def centroids(self) -> torch.Tensor:
+        """(nlist, d) fp32; the quantiser compares against their bf16 roundings."""
+        self._require_trained()
+        return self._centroids
+
+    def _require_trained(self) -> None:
+        if self._centroids is None:
+            raise RuntimeError("IVFFlatIndex has no centroids yet: call train() first")
+
+    def train(self, x=None, max_iter: int = 25, sample: Optional[int] = None, centroids=None) -> None:
+        """Fit the nlist centroids to x (n >= nlist rows) with spherical k-means (contrastors_amd.cluster.KMeans, seeded: the
+        same x and seed give the same bits; sample: fit on a seeded subsample), or take a given (nlist, d) table as it is."""
+        if (x is None) == (centroids is None):
+            raise ValueError("train: give either the training rows or centroids=")
+        if self.ntotal:
+            raise RuntimeError("train: the index holds rows labelled by the current centroids; reset() first")
+        if centroids is not None:
+            if tuple(np.shape(centroids)) != (self.nlist, self.d):
+                raise ValueError(f"expected ({self.nlist}, {self.d}) centroids, got shape {tuple(np.shape(centroids))}")
+            c = torch.as_tensor(centroids).to(device=self.device, dtype=torch.float32).clone()
+        else:
+            from .cluster import KMeans
+
+            km = KMeans(self.nlist, self.d, spherical=True, device=self.device, seed=self.seed)
+            c = km.fit(x, max_iter=int(max_iter), sample=sample).centroids
+        self._centroids = c
+        self._coarse = FlatIPIndex(self.d, device=self.device, workspace_bytes=self.workspace_bytes)
+        self._coarse.add(c)
+
+    def add(self, x) -> None:
+        """Append rows (rounded to bf16 as FlatIPIndex.add rounds); row i of the n-th add gets id ntotal + i.  Every row is
+        labelled with the list of its largest inner product over the centroids' bf16 roundings, ties to the lower list
+        (cx_kmeans_assign without a bias): the first probe the coarse search returns for the same vector."""
+        self._require_trained()
+        xb = _to_device_2d(x, self.d, self.device)
+        if isinstance(x, torch.Tensor) and xb.data_ptr() == x.data_ptr():
+            xb = xb.clone()
+        n = xb.shape[0]
+        if self.ntotal + n > MAX_NTOTAL:
+            raise ValueError(f"IVFFlatIndex holds at most {MAX_NTOTAL} vectors")
+        if n == 0:
+            return
+        labels = torch.empty(n, dtype=torch.int32, device=self.device)
+        best = torch.empty(n, dtype=torch.float32, device=self.device)
+        C = self._coarse.vectors
+        with torch.cuda.device(self.device):
+            _C.check(_C.lib().cx_kmeans_assign(xb.data_ptr(), C.data_ptr(), None, n, self.nlist, self.d, self.d, self.d,
+                                               labels.data_ptr(), best.data_ptr(), None, _C.cur_stream()), "cx_kmeans_assign")
+        self._pending.append((xb, labels))
+        self.ntotal += n
+
+    def _finalise(self) -> None:
+        """Sort what was added since the last search into the lists.  The sorted rows and the new chunks are concatenated
+        (sorted rows keep ascending ids per list and new ids are larger, so one stable sort by label restores the invariant),
+        the sources are released, and the rows are gathered into list order: twice the corpus at the peak."""
+        if not self._pending:
+            return
+        from .dedup import label_order
+
+        n_old = 0 if self._rows is None else self._rows.shape[0]
+        rows = ([self._rows] if n_old else []) + [r for r, _ in self._pending]
+        labs = ([self._labels] if n_old else []) + [l for _, l in self._pending]
+        ids = ([self._order] if n_old else []) + [torch.arange(n_old, self.ntotal, dtype=torch.int64, device=self.device)]
+        self._rows, self._pending = None, []
+        x = rows[0] if len(rows) == 1 else torch.cat(rows)
+        del rows
+        lab = labs[0] if len(labs) == 1 else torch.cat(labs)
+        ids = ids[0] if len(ids) == 1 else torch.cat(ids)
+        perm = torch.from_numpy(label_order(lab.cpu().numpy())).to(self.device)
+        self._rows = x[perm]
+        del x
+        self._labels = lab[perm]
+        self._order = ids[perm]
+        self._inv = torch.empty_like(self._order)
+        self._inv[self._order] = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
+        self._list_ptr = torch.searchsorted(self._labels, torch.arange(self.nlist + 1, dtype=torch.int32, device=self.device)
+                                            ).to(torch.int64)
+
+    @property
+    def list_sizes(self) -> torch.Tensor:
+        """(nlist,) int64: rows per list."""
+        self._require_trained()
+        if not self.ntotal:
+            return torch.zeros(self.nlist, dtype=torch.int64, device=self.device)
+        self._finalise()
+        return self._list_ptr[1:] - self._list_ptr[:-1]
+
+    def batch_queries(self, M: int, k: int, nprobe: int) -> int:
+        """Queries per launch: their nprobe pair rows each hold a gathered query, a (k) list in the kernel's workspace and one
+        in the merge's input; as many (all of M, else a multiple of 128, at least one) as fit workspace_bytes."""
+        per_pair = k * 12 + k * 8 + 4 + 2 * self.d + 32
+        m = self.workspace_bytes // (nprobe * per_pair)
+        if m >= 128:
+            m = m // 128 * 128
+        return max(1, min(M, m))
+
+    def search(self, queries, k: int, nprobe: int, exclude=None, below=None):
+        """-> (scores (M, k) float32, ids (M, k) int64), the conventions of FlatIPIndex.search (descending score, ties to the
+        lower id, (-inf, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows of
+        the nprobe lists nearest to each query, 1 <= nprobe <= min(nlist, 256).  ids, and the ids of exclude, are the ids
+        add() gave.  nprobe == nlist is the exact search, bit for bit."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        k, nprobe = int(k), int(nprobe)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        if not 1 <= nprobe <= min(self.nlist, MAX_NPROBE):
+            raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(self.nlist, MAX_NPROBE)}], got {nprobe}")
+        self._require_trained()
+        q = _to_device_2d(queries, self.d, self.device)
+        M = q.shape[0]
+        row_ptr, xhost = _exclusion_csr_host(exclude, M)
+        bel = None
+        if below is not None:
+            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
+            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+            if bel.numel() != M:
+                raise ValueError(f"below has {bel.numel()} entries for {M} queries")
+        scores = torch.full((M, k), -float("inf"), dtype=torch.float32, device=self.device)
+        ids = torch.full((M, k), -1, dtype=torch.int64, device=self.device)
+        if M and self.ntotal:
+            self._finalise()
+            h = _C.lib()
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                probes = self._coarse.search(q, nprobe)[1]
+                dptr = xids = None
+                if row_ptr is not None and xhost.numel():
+                    dptr, xids = row_ptr.to(self.device), xhost.to(self.device)
+                mq = self.batch_queries(M, k, nprobe)
+                for b0 in range(0, M, mq):
+                    m = min(mq, M - b0)
+                    P = m * nprobe
+                    pair_q, mid, end, src = ivf_pair_plan(probes[b0: b0 + m], self._list_ptr)
+                    qg = q[b0: b0 + m][pair_q]
+                    bg = None if bel is None else bel[b0: b0 + m][pair_q]
+                    pptr = pids = None
+                    if dptr is not None:
+                        e0, e1 = int(row_ptr[b0]), int(row_ptr[b0 + m])      # (host copies)
+                        if e1 > e0:
+                            pptr, pids = ivf_pair_exclusions(dptr[b0: b0 + m + 1] - e0, xids[e0: e1], pair_q, self._inv, nprobe)
+                    ws = torch.empty(h.cx_search_window_ws_bytes(P, k), dtype=torch.uint8, device=self.device)
+                    ls = torch.empty(P, k, dtype=torch.float32, device=self.device)
+                    li = torch.empty(P, k, dtype=torch.int64, device=self.device)
+                    _C.check(h.cx_search_window_topk(qg.data_ptr(), self._rows.data_ptr(), P, self.ntotal, self.d, self.d,
+                                                     self.d, k, mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
+                                                     _C.ptr(bg), ws.data_ptr(), ls.data_ptr(), li.data_ptr(), stream),
+                             "cx_search_window_topk")
+                    _C.check(h.cx_topk_merge_lists(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
+                                                   self._order.data_ptr(), self.ntotal, scores[b0].data_ptr(),
+                                                   ids[b0].data_ptr(), stream), "cx_topk_merge_lists")
+        if as_numpy:
+            return scores.cpu().numpy(), ids.cpu().numpy()
+        return scores, ids
 
 
 MAX_CANDIDATES = 4096            # cx_rescore_topk's candidate-list bound

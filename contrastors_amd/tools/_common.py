@@ -92,19 +92,51 @@ def add_search_arguments(ap) -> None:
                          "the memory-mapped document .npy")
     ap.add_argument("--rescore_factor", type=int, default=4,
                     help="binary: candidates re-scored per returned neighbour (k * rescore_factor, at most 4096)")
+    ap.add_argument("--ivf_lists", type=int, default=0,
+                    help="exact: search inside K k-means lists of the corpus instead of all of it (IVFFlatIndex); 0 = off")
+    ap.add_argument("--ivf_nprobe", type=int, default=None,
+                    help="lists probed per query, at most min(K, 256) (default: min(8, K)); K probes give the exact result")
+    ap.add_argument("--ivf_centroids", default=None, help="(K, d) .npy centroid table to use instead of fitting one")
+    ap.add_argument("--ivf_sample", type=int, default=None, help="fit the centroids on that many sampled documents")
+    ap.add_argument("--ivf_iters", type=int, default=25, help="k-means iterations of the fit")
+
+
+def check_search_arguments(ap, args) -> dict:
+    """Refuse flag combinations the search cannot serve (ap.error) -> the ivf_* keyword arguments of search()."""
+    if args.ivf_lists < 0:
+        ap.error("--ivf_lists must not be negative")
+    if args.ivf_lists == 0:
+        if args.ivf_nprobe is not None or args.ivf_centroids is not None or args.ivf_sample is not None:
+            ap.error("--ivf_nprobe, --ivf_centroids and --ivf_sample need --ivf_lists K")
+        return {}
+    if args.coarse != "exact":
+        ap.error("--ivf_lists goes with --coarse exact only")
+    nprobe = min(8, args.ivf_lists) if args.ivf_nprobe is None else args.ivf_nprobe
+    if not 1 <= nprobe <= min(args.ivf_lists, 256):
+        ap.error(f"--ivf_nprobe must be in [1, {min(args.ivf_lists, 256)}]")
+    if args.ivf_iters < 1 or (args.ivf_sample is not None and args.ivf_sample < 1):
+        ap.error("--ivf_iters and --ivf_sample must be positive")
+    return {"ivf_lists": args.ivf_lists, "ivf_nprobe": nprobe, "ivf_centroids": args.ivf_centroids,
+            "ivf_sample": args.ivf_sample, "ivf_iters": args.ivf_iters}
 
 
 def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, coarse: str = "exact",
-           rescore_factor: int = 4):
+           rescore_factor: int = 4, ivf_lists: int = 0, ivf_nprobe: Optional[int] = None, ivf_centroids=None,
+           ivf_sample: Optional[int] = None, ivf_iters: int = 25):
     """-> (scores, ids) numpy.  coarse="exact": exact inner-product top-k over the bf16 corpus (FlatIPIndex).
     coarse="binary": Hamming top-(k * rescore_factor) over sign codes (BinaryFlatIndex), re-scored exactly against doc_emb,
-    which stays on the host (an array or a memmap); equal to "exact" once the candidates cover the corpus."""
+    which stays on the host (an array or a memmap); equal to "exact" once the candidates cover the corpus.
+    ivf_lists = K > 0 (with "exact"): the top-k of the ivf_nprobe (default min(8, K)) nearest of K k-means lists
+    (IVFFlatIndex; centroids fitted to doc_emb with ivf_iters iterations on ivf_sample rows, or read from the .npy path /
+    array ivf_centroids); equal to "exact" when every list is probed."""
     import torch
 
-    from ..search import BinaryFlatIndex, FlatIPIndex, search_binary_rescored
+    from ..search import BinaryFlatIndex, FlatIPIndex, IVFFlatIndex, search_binary_rescored
 
     if coarse not in COARSE:
         raise ValueError(f"coarse must be one of {COARSE}, got {coarse!r}")
+    if ivf_lists and coarse != "exact":
+        raise ValueError("ivf_lists goes with coarse='exact' only")
     if coarse == "binary":
         n, d = np.shape(doc_emb)
         index = BinaryFlatIndex(d, device=device)
@@ -113,6 +145,17 @@ def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, co
             index.add(torch.as_tensor(np.asarray(doc_emb[r0: r0 + ADD_ROWS], dtype=np.float32)))
         return search_binary_rescored(index, doc_emb, np.asarray(query_emb, dtype=np.float32), k, rescore_factor,
                                       exclude=exclude, below=below)
+    if ivf_lists:
+        docs = torch.as_tensor(np.asarray(doc_emb, dtype=np.float32))
+        index = IVFFlatIndex(np.shape(doc_emb)[1], int(ivf_lists), device=device)
+        if ivf_centroids is not None:
+            table = np.load(ivf_centroids) if isinstance(ivf_centroids, (str, Path)) else ivf_centroids
+            index.train(centroids=np.asarray(table, dtype=np.float32))
+        else:
+            index.train(docs, max_iter=ivf_iters, sample=ivf_sample)
+        index.add(docs)
+        nprobe = min(8, int(ivf_lists)) if ivf_nprobe is None else int(ivf_nprobe)
+        return index.search(np.asarray(query_emb, dtype=np.float32), k, nprobe, exclude=exclude, below=below)
     index = FlatIPIndex(np.shape(doc_emb)[1], device=device)
     index.add(torch.as_tensor(np.asarray(doc_emb, dtype=np.float32)))
     return index.search(np.asarray(query_emb, dtype=np.float32), k, exclude=exclude, below=below)

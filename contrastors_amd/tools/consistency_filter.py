@@ -18,7 +18,7 @@ from typing import List
 
 import numpy as np
 
-from ._common import add_search_arguments, encode_texts, load_npy, search
+from ._common import add_search_arguments, check_search_arguments, encode_texts, load_npy, search
 
 
 def keep_ids(ids: List, top_k_indices) -> List:
@@ -31,10 +31,11 @@ def keep_ids(ids: List, top_k_indices) -> List:
 
 
 def filter_pairs(ids: List, q_emb, d_emb, device: str = "cuda", k: int = 2, coarse: str = "exact",
-                 rescore_factor: int = 4) -> List:
-    """ids[i] names pair i; -> the kept ids, in ascending id order."""
+                 rescore_factor: int = 4, **ivf) -> List:
+    """ids[i] names pair i; -> the kept ids, in ascending id order.  ivf: the ivf_* arguments of _common.search."""
     pos = sorted(range(len(ids)), key=lambda i: ids[i])
-    _, top = search(np.asarray(d_emb)[pos], np.asarray(q_emb)[pos], k, device, coarse=coarse, rescore_factor=rescore_factor)
+    _, top = search(np.asarray(d_emb)[pos], np.asarray(q_emb)[pos], k, device, coarse=coarse, rescore_factor=rescore_factor,
+                    **ivf)
     return keep_ids(ids, top)
 
 
@@ -74,6 +75,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     if not 1 <= args.k <= 1024:
         ap.error("--k must be in [1, 1024]")
+    ivf = check_search_arguments(ap, args)
     if (args.query_embeddings is None) != (args.document_embeddings is None):
         ap.error("give both --query_embeddings and --document_embeddings, or neither")
     if args.query_embeddings:
@@ -94,7 +96,7 @@ def main(argv=None) -> int:
                          args.max_length, args.device).cpu().numpy()
     if len(set(ids)) != len(ids):
         ap.error("pair ids must be unique")
-    kept = filter_pairs(ids, q, d, args.device, args.k, args.coarse, args.rescore_factor)
+    kept = filter_pairs(ids, q, d, args.device, args.k, args.coarse, args.rescore_factor, **ivf)
     out = Path(args.output_dir)
     out.mkdir(parents=True, exist_ok=True)
     n_existing = len(list(out.glob("ids_to_keep_*.json")))

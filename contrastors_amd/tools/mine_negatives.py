@@ -37,7 +37,7 @@ from typing import Dict, List
 
 import numpy as np
 
-from ._common import add_search_arguments, encode_texts, load_npy, search, triplet_metadata, write_shards
+from ._common import add_search_arguments, check_search_arguments, encode_texts, load_npy, search, triplet_metadata, write_shards
 
 DEVIATIONS = """deviations from the reference scripts:
   the random fill (topk) and the record shuffle (margin) are seeded by --seed;
@@ -231,6 +231,7 @@ def main(argv=None) -> int:
         ap.error("--max_negatives is at most 1024")
     if not Path(args.dataset).exists():
         ap.error(f"--dataset {args.dataset} does not exist")
+    ivf = check_search_arguments(ap, args)
     if (args.query_embeddings is None) != (args.document_embeddings is None):
         ap.error("give both --query_embeddings and --document_embeddings, or neither")
     if args.query_ids and (topk or args.query_embeddings is None):
@@ -241,7 +242,7 @@ def main(argv=None) -> int:
     if topk:
         queries, documents, records = load_records(args.dataset, args.query_key, args.document_key, args.negatives_key)
         q_emb, d_emb = _embeddings(args, queries, documents)
-        _, indices = search(d_emb, q_emb, args.k, args.device, coarse=args.coarse, rescore_factor=args.rescore_factor)
+        _, indices = search(d_emb, q_emb, args.k, args.device, coarse=args.coarse, rescore_factor=args.rescore_factor, **ivf)
         records = select_topk(records, documents, indices, args.k, args.query_key, args.document_key,
                               args.negatives_key, np.random.RandomState(args.seed))
         write_shards(records, args.output_dir, meta)
@@ -263,7 +264,7 @@ def main(argv=None) -> int:
         q_emb, d_emb = _embeddings(args, list(queries.values()), documents)
     pairs, rows, excl, below = margin_pairs(qrels, qid2index, docid2index, q_emb, d_emb, args.margin)
     _, indices = search(d_emb, np.asarray(q_emb)[rows], args.max_negatives, args.device, exclude=excl, below=below,
-                        coarse=args.coarse, rescore_factor=args.rescore_factor)
+                        coarse=args.coarse, rescore_factor=args.rescore_factor, **ivf)
     mined, dropped = select_margin(pairs, indices, corpus, queries, documents, args.k, args.query_key,
                                    args.document_key, args.negatives_key)
     random.Random(args.seed).shuffle(mined)

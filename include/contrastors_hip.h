@@ -370,6 +370,26 @@ long cx_search_ws_bytes(int M, long N, int k, int nsplit);
 int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
                    const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, int nsplit, void* ws,
                    float* out_scores, int64_t* out_ids, void* stream);
+/* ---- top-k inside a per-row id window, and a merge of top-k lists (what an IVF index is made of; csrc/search.hip).
+ *          Additive: cx_abi_version stays 10. ------------------------------------------------------------------------------
+ * cx_search_window_topk: cx_search_topk (same operands, alignment rules, error codes, order, padding, score bits) where row m
+ * admits document n only if min_id[m] < n < end_id[m]; min_id / end_id:(M) int64 device arrays, clamped to [-1, N] and [0, N],
+ * NULL = -1 / N everywhere.  excl_ids and out_ids are corpus positions.  A 128-row query tile computes only the corpus tiles
+ * [t0, t1), t0 = (min min_id + 1) / 128 and t1 = ceil(max end_id / 128) over its rows with a non-empty window (a tile without
+ * one computes nothing), in one workgroup: made for rows sorted by window.  ws: 16-B aligned,
+ * cx_search_window_ws_bytes(M, k) bytes, need not be initialised.  Deterministic, no atomics on global memory.
+ * cx_topk_merge_lists: scores / ids:(P,k) = P sorted top-k lists padded with (-inf, -1) (a list ends at its first negative
+ * id), as the two search entry points write them.  src:(M,L) int64 names the lists of output row m; entries outside [0, P)
+ * are skipped; 1 <= L <= 256.  id_map:(N) int64 or NULL: the id reported for position n is id_map[n] (NULL: n; N is read only
+ * with id_map).  out_scores / out_ids:(M,k) = the k best entries of the row's lists by (score descending, REPORTED id
+ * ascending), padded with (-inf, -1).  The lists of one row must be disjoint and each sorted in that order (true when id_map
+ * ascends along every list).  Rank counting: every output slot is written once, no atomics, deterministic. */
+long cx_search_window_ws_bytes(int M, int k);
+int cx_search_window_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
+                          const int64_t* min_id, const int64_t* end_id, const int64_t* excl_ptr, const int64_t* excl_ids,
+                          const float* below, void* ws, float* out_scores, int64_t* out_ids, void* stream);
+int cx_topk_merge_lists(const float* scores, const int64_t* ids, long P, int k, const int64_t* src, int M, int L,
+                        const int64_t* id_map, long N, float* out_scores, int64_t* out_ids, void* stream);
 /* ---- rank of target columns in the rows of the similarity matrix (zero-shot top-k accuracy, retrieval recall@k:
  *          sc/trainers/image_text.py:198-254; csrc/rank.hip).  Additive: cx_abi_version stays 10. ------------------------------
  * Q, D, d, ldq, ldd, N: as cx_search_topk (same alignment rules and error codes).  tgt_ptr:(M+1) / tgt_ids: int64 CSR lists
