@@ -22,6 +22,10 @@
 // sorted by list, (query, probed list) pairs sorted by list, so that a 128-pair tile walks a short run of consecutive lists.
 // cx_topk_merge_lists is stage 2 behind an indirection: the lists of an output row are named by src and live in (P, k) score /
 // id arrays as the search entry points write them; ids may be mapped on the way out (list positions -> original ids).
+//
+// cx_search_int8_topk is stage 1 over int8 codes with one fp32 scale per row (search_int8_tiles_kernel, below the bf16 kernel):
+// its own operand staging, K loop (v_mfma_i32_16x16x64_i8) and scaling epilogue; Cand, SearchLds, insert_row<false>,
+// merge_lists_kernel<SplitLists> and auto_splits are shared as they are.
 #include <type_traits>
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
@@ -300,6 +304,139 @@ template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kerne
     if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
 }
 
+// ---- int8 scalar-quantised rows (cx_search_int8_topk) -----------------------------------------------------------------
+// Stage 1 over int8 codes with one fp32 scale per row: acc = sum_j Q[m][j] D[n][j] on v_mfma_i32_16x16x64_i8 (exact in int32;
+// |acc| <= 127^2 * 1024 < 2^24, so (float)acc is exact too) and s = ((float)acc * d_scale[n]) * q_scale[m], two fp32
+// multiplications in that order.  The operands are issued as in search_tiles_kernel (A := document rows, B := query rows), so
+// the accumulator layout, the threshold test, the fp32 tile in LDS, insert_row<false> and the split merge are that kernel's.
+// A K chunk is 128 bytes per row = 128 K elements in the same poff swizzle; the 16 bytes a lane feeds to one MFMA are the same
+// K positions for both operands, which is all an integer dot product needs.  d % 128 == 64: the last chunk is half used; its
+// upper half is staged from the lower half's addresses (never past the row) and the K loop does not read it.
+typedef __attribute__((ext_vector_type(4))) int i32x4_t;
+constexpr int BK8 = 128;             // int8 K elements (= bytes) per row of a panel: PANEL = TM * BK8 as well
+
+struct Int8Params : SearchParams {   // (Q, D of the base stay null; ldq / ldd count bytes)
+    const int8_t* Q8;
+    const int8_t* D8;
+    const float* q_scale;  // (M)
+    const float* d_scale;  // (N)
+};
+
+struct Int8SearchLds : SearchLds {
+    alignas(16) float dsc[TN];    // the scales of the current corpus tile's rows (read four at a time)
+    float qsc[TM];                // ... and of the query tile's rows
+};
+
+CX_DEVICE void stage8(const Int8Params& p, int m0, int n0, int k0, int tid, uint4 (&sq)[4], uint4 (&sd)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int item = tid + 256 * i, r = item >> 3, c = item & 7;
+        const int gm = min(m0 + r, p.M - 1), gn = min(n0 + r, p.N - 1);   // clamped rows are read but never admitted
+        int kb = k0 + c * 16;
+        if (kb >= p.d) kb -= 64;   // the unused half of the last chunk: any bytes of the row
+        sq[i] = *reinterpret_cast<const uint4*>(p.Q8 + (int64_t)gm * p.ldq + kb);
+        sd[i] = *reinterpret_cast<const uint4*>(p.D8 + (int64_t)gn * p.ldd + kb);
+    }
+}
+
+__global__ __launch_bounds__(256, 1) void search_int8_tiles_kernel(Int8Params p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    Int8SearchLds& L = *reinterpret_cast<Int8SearchLds*>(dsm);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
+    const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
+    const int m0 = tm * TM;
+    const int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
+    const int nk = (p.d + BK8 - 1) / BK8;
+
+    if (tid < TM) {
+        const int m = m0 + tid;
+        L.thr[tid] = m < p.M ? -INFINITY : INFINITY;   // rows past M never pass the threshold test
+        L.bel[tid] = (m < p.M && p.below) ? p.below[m] : INFINITY;
+        L.qsc[tid] = p.q_scale[min(m, p.M - 1)];
+        L.cnt[tid] = 0;
+        L.flag[tid] = 0;
+    }
+    if (tid == 0) L.any = 0;
+    __syncthreads();
+
+    for (int t = t_begin; t < t_end; ++t) {
+        const int n0 = t * TN;
+        if (tid < TN) L.dsc[tid] = p.d_scale[min(n0 + tid, p.N - 1)];   // read in the epilogue, behind the K loop's barriers
+        i32x4_t acc[4][4];   // [query block qb][document block db]
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = i32x4_t{0, 0, 0, 0};
+        uint4 sq[4], sd[4];
+        stage8(p, m0, n0, 0, tid, sq, sd);
+        commit(L.ops, L.ops + PANEL, tid, sq, sd);
+        __syncthreads();
+        for (int kc = 0; kc < nk; ++kc) {
+            const char* qb_ = L.ops + (kc & 1) * 2 * PANEL;
+            const char* db_ = qb_ + PANEL;
+            stage8(p, m0, n0, min(kc + 1, nk - 1) * BK8, tid, sq, sd);   // the last chunk is staged twice (unconditional)
+            const int nks = (p.d - kc * BK8) > 64 ? 2 : 1;
+            for (int ks = 0; ks < nks; ++ks) {
+                i32x4_t fq[4], fd[4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    fq[b] = *reinterpret_cast<const i32x4_t*>(qb_ + poff(wq * 64 + b * 16 + l15, ks * 4 + lh));
+                    fd[b] = *reinterpret_cast<const i32x4_t*>(db_ + poff(wd * 64 + b * 16 + l15, ks * 4 + lh));
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        acc[a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fd[b], fq[a], acc[a][b], 0, 0, 0);
+            }
+            char* nq = L.ops + ((kc + 1) & 1) * 2 * PANEL;
+            commit(nq, nq + PANEL, tid, sq, sd);
+            __syncthreads();
+        }
+
+        // acc[a][b][r] = the integer dot product of (query m0 + wq*64 + a*16 + l15, document n0 + wd*64 + b*16 + 4*lh + r)
+        f32x4_t sc[4][4];
+        bool hit = false;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int row = wq * 64 + a * 16 + l15;
+            const float thr = L.thr[row], bel = L.bel[row], qs = L.qsc[row];
+            bool h = false;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const f32x4_t ds = *reinterpret_cast<const f32x4_t*>(&L.dsc[wd * 64 + b * 16 + 4 * lh]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = __fmul_rn(__fmul_rn((float)acc[a][b][r], ds[r]), qs);
+                    sc[a][b][r] = v;
+                    h |= (v > thr) & (v < bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
+                }
+            }
+            if (h) L.flag[row] = 1;
+            hit |= h;
+        }
+        if (hit) L.any = 1;
+        __syncthreads();
+        if (L.any) {
+            float* tile = reinterpret_cast<float*>(L.ops);   // the operand buffers are free until the next tile
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    *reinterpret_cast<f32x4_t*>(tile + (wq * 64 + a * 16 + l15) * TN + wd * 64 + b * 16 + 4 * lh) = sc[a][b];
+            __syncthreads();
+            for (int row = wave; row < TM; row += 4)
+                if (L.flag[row]) insert_row<false>(p, L, tile, row, m0 + row, n0, split, wave, lane);
+            __syncthreads();
+            if (tid < TM) L.flag[tid] = 0;
+            if (tid == 0) L.any = 0;
+        }
+        __syncthreads();
+    }
+    if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
+}
+
 constexpr int MAXLISTS = 256;       // lists merged into one output row (>= MAXSPLIT)
 
 // What the merge orders: (score, reported id).  int64 ids: the reported id of cx_topk_merge_lists is any int64 of id_map.
@@ -444,6 +581,42 @@ int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, l
         if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
     }
     // N == 0: counts stays null and every row is padding
+    const SplitLists S = {lists, counts, ns, k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_search_int8_ws_bytes(int M, long N, int k, int nsplit) { return cx_search_ws_bytes(M, N, k, nsplit); }
+
+int cx_search_int8_topk(const int8_t* Q, const int8_t* D, const float* q_scale, const float* d_scale, int M, long N, int d,
+                        long ldq, long ldd, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
+                        int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Q || !q_scale || !out_scores || !out_ids || (N > 0 && (!D || !d_scale || !ws)) || (excl_ptr && !excl_ids))
+        return CX_ERR_ARG;
+    if (ldq < d || (ldq % 16) != 0 || (N > 0 && (ldd < d || (ldd % 16) != 0))) return CX_ERR_ALIGN;
+    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
+    Cand* lists = reinterpret_cast<Cand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
+    if (N > 0) {
+        Int8Params p = {};
+        p.Q8 = Q; p.D8 = D; p.q_scale = q_scale; p.d_scale = d_scale; p.ldq = ldq; p.ldd = ldd;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = ns;
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
+        p.lists = lists; p.counts = counts;
+        const int tiles_m = (M + TM - 1) / TM;
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel), (int)sizeof(Int8SearchLds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_int8_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(Int8SearchLds), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
     const SplitLists S = {lists, counts, ns, k};
     hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
                        out_ids);

@@ -17,6 +17,10 @@ cx_search_window_topk / cx_topk_merge_lists); with every list probed it is `Flat
 trained with `hamming: true`; `rescore` / `search_binary_rescored` re-score its candidates exactly against the bf16 rows,
 which may stay on the host or in a memory-mapped file (csrc/search_binary.hip).
 
+`Int8FlatIndex` is the format in between (faiss SQ8, sentence-transformers "int8"): d int8 codes + one fp32 scale per row
+(`quantize_rows_int8`, csrc/quantize_int8.hip), searched with an exact integer dot product on the matrix cores
+(cx_search_int8_topk, csrc/search.hip); `search_int8_rescored` re-scores its candidates exactly like the binary pipeline.
+
 `encode` is the embedding side: this project's BiEncoder under no_grad, length-sorted batches, results in input order.
 """
 from __future__ import annotations
@@ -887,25 +891,11 @@ def rescore(queries, cand_ids, vectors, k: int, below=None, device=None):
     return scores, ids
 
 
-def search_binary_rescored(index: BinaryFlatIndex, vectors, queries, k: int, rescore_factor: int = 4, exclude=None,
-                           below=None):
-    """Coarse Hamming search + exact re-scoring: the min(k * rescore_factor, 4096) nearest codes of `index` per query, then
-    the k best of those by exact inner product with `vectors` (the corpus the codes were made from: see rescore).  exclude
-    applies to the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it when the
-    candidate lists cover the corpus.  Lists longer than the Hamming kernel's k bound (1024) are fetched in pages of 1024,
-    each page excluding the ones before it (the order is strict, so the pages are the consecutive runs of one ranking)."""
-    k = int(k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-    if int(rescore_factor) < 1:
-        raise ValueError(f"rescore_factor must be at least 1, got {rescore_factor}")
-    if np.shape(vectors)[0] != index.ntotal:
-        raise ValueError(f"{np.shape(vectors)[0]} vectors for an index of {index.ntotal} codes")
-    as_numpy = not isinstance(queries, torch.Tensor)
-    c = max(k, min(k * int(rescore_factor), MAX_CANDIDATES))
-    M = int(np.shape(queries)[0])
-    qd = _to_device_2d(queries, index.d, index.device)
-    qc = pack_sign_bits(qd)
+def _paged_candidates(search_page, M: int, c: int, ntotal: int, exclude) -> torch.Tensor:
+    """-> (M, <= c) int64 ids: the first c entries of a coarse ranking whose kernel returns at most 1024 per call.
+    search_page(kp, exclude) -> the (M, kp) ids of the top kp under `exclude`.  Lists longer than 1024 are fetched in pages of
+    1024, each page excluding the ones before it (the order is strict, so the pages are the consecutive runs of one ranking);
+    the loop stops once the pages cover the index."""
     xptr, xids = _exclusion_csr_host(exclude, M)
     pages = []
     for p0 in range(0, c, MAX_K):
@@ -919,17 +909,298 @@ def search_binary_rescored(index: BinaryFlatIndex, vectors, queries, k: int, res
             ptr = torch.zeros(M + 1, dtype=torch.int64)
             ptr[1:] = torch.cumsum(torch.as_tensor([len(r) for r in rows], dtype=torch.int64), 0)
             ex = (ptr.numpy(), (torch.cat(rows) if rows else prev[:0, 0]).numpy())
-        pages.append(index.search(qc, kp, exclude=ex)[1])
-        if index.ntotal <= p0 + kp:
+        pages.append(search_page(kp, ex))
+        if ntotal <= p0 + kp:
             break
-    cand = torch.cat(pages, 1) if len(pages) > 1 else pages[0]
-    s, i = rescore(qd, cand, vectors, min(k, cand.shape[1]), below=below, device=index.device)
+    return torch.cat(pages, 1) if len(pages) > 1 else pages[0]
+
+
+def _rescore_candidates(qd, cand, vectors, k: int, below, device, as_numpy: bool):
+    """The exact stage of a two-stage search: rescore() of the candidate lists, padded to k columns."""
+    M = cand.shape[0]
+    s, i = rescore(qd, cand, vectors, min(k, cand.shape[1]), below=below, device=device)
     if s.shape[1] < k:    # fewer candidates than k: an index smaller than k
         s = torch.cat([s, torch.full((M, k - s.shape[1]), -float("inf"), dtype=s.dtype, device=s.device)], 1)
         i = torch.cat([i, torch.full((M, k - i.shape[1]), -1, dtype=i.dtype, device=i.device)], 1)
     if as_numpy:
         return s.cpu().numpy(), i.cpu().numpy()
     return s, i
+
+
+def _check_rescored_arguments(index, vectors, k: int, rescore_factor: int) -> int:
+    """-> the candidate count c of a two-stage search (refusals first)."""
+    if not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+    if int(rescore_factor) < 1:
+        raise ValueError(f"rescore_factor must be at least 1, got {rescore_factor}")
+    if np.shape(vectors)[0] != index.ntotal:
+        raise ValueError(f"{np.shape(vectors)[0]} vectors for an index of {index.ntotal} codes")
+    return max(k, min(k * int(rescore_factor), MAX_CANDIDATES))
+
+
+def search_binary_rescored(index: BinaryFlatIndex, vectors, queries, k: int, rescore_factor: int = 4, exclude=None,
+                           below=None):
+    """Coarse Hamming search + exact re-scoring: the min(k * rescore_factor, 4096) nearest codes of `index` per query, then
+    the k best of those by exact inner product with `vectors` (the corpus the codes were made from: see rescore).  exclude
+    applies to the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it when the
+    candidate lists cover the corpus.  Lists longer than the Hamming kernel's k bound (1024) are fetched in pages
+    (_paged_candidates)."""
+    k = int(k)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    as_numpy = not isinstance(queries, torch.Tensor)
+    M = int(np.shape(queries)[0])
+    qd = _to_device_2d(queries, index.d, index.device)
+    qc = pack_sign_bits(qd)
+    cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+
+
+INT8_ZERO_AMAX = 2.0 ** -100     # rows whose largest magnitude is below this quantise to zero codes and a zero scale
+QUANTIZE_ROWS = 1 << 16          # Int8FlatIndex.add: float rows uploaded and quantised per step
+
+
+def _quantize_rows_numpy(a: np.ndarray):
+    """The contract of cx_quantize_rows_int8 in numpy: every step one IEEE fp32 operation."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    amax = np.abs(a).max(axis=1) if a.shape[0] else np.zeros(0, dtype=np.float32)
+    zero = ~(amax >= np.float32(INT8_ZERO_AMAX))
+    safe = np.where(zero, np.float32(1), amax).astype(np.float32)
+    with np.errstate(all="ignore"):
+        inv = np.where(zero, np.float32(0), np.float32(127) / safe).astype(np.float32)
+        scale = np.where(zero, np.float32(0), safe / np.float32(127)).astype(np.float32)
+        codes = np.clip(np.rint(a * inv[:, None]), np.float32(-127), np.float32(127))
+        codes = np.where(np.isnan(codes), np.float32(-127), codes).astype(np.int8)
+    return codes, scale
+
+
+def _quantize_rows_device(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> None:
+    """x (n, d) fp32 / bf16 on the GPU (unit column stride) -> codes (n, d) int8 and scales (n) fp32 views, in place."""
+    n, d = x.shape
+    if n:
+        with torch.cuda.device(x.device):
+            _C.check(_C.lib().cx_quantize_rows_int8(x.data_ptr(), 0 if x.dtype == torch.float32 else 1, n, d,
+                                                    x.stride(0) if n > 1 else d, codes.data_ptr(), codes.stride(0) if n > 1 else d,
+                                                    scales.data_ptr(), _C.cur_stream()), "cx_quantize_rows_int8")
+
+
+def _quantizable(x: torch.Tensor) -> torch.Tensor:
+    """A GPU tensor as the kernel takes it: fp32 or bf16 (other dtypes as fp32), unit column stride, rows not overlapping."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x
+
+
+def quantize_rows_int8(x):
+    """Per-row symmetric int8 codes of the rows of x (n, d) -> (codes int8 (n, d), scales float32 (n,)), x ~ codes * scale:
+    sentence-transformers' "int8" precision / faiss SQ8 with one range per row.  amax = max |x_j| in fp32; a row with
+    amax < 2^-100 gets zero codes and scale 0; otherwise scale = amax / 127 and code_j = clamp(rint(x_j * (127 / amax)), -127,
+    127), every step one IEEE fp32 operation with round-half-to-even (-128 never occurs).  A tensor on the GPU goes through
+    cx_quantize_rows_int8 (fp32 and bf16 as they are, other dtypes as fp32; a row stride is honoured); a CPU tensor or a numpy
+    array through numpy.  Same bytes either way for finite input; torch in -> torch out.  Non-finite input never faults and is
+    otherwise unspecified: the kernel skips NaN in the maximum and gives a NaN product the code -127, numpy turns a row that
+    holds a NaN into a zero row; an infinite element gives scale inf either way."""
+    is_torch = isinstance(x, torch.Tensor)
+    if not is_torch:
+        x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError(f"expected a (n, d) array, got shape {tuple(x.shape)}")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    _check_code_dim(d)
+    if not is_torch or x.device.type != "cuda":
+        codes, scales = _quantize_rows_numpy(x.float().numpy() if is_torch else x)
+        return (torch.from_numpy(codes), torch.from_numpy(scales)) if is_torch else (codes, scales)
+    codes = torch.empty(n, d, dtype=torch.int8, device=x.device)
+    scales = torch.empty(n, dtype=torch.float32, device=x.device)
+    _quantize_rows_device(_quantizable(x), codes, scales)
+    return codes, scales
+
+
+def _is_code_pair(x) -> bool:
+    return isinstance(x, tuple) and len(x) == 2
+
+
+class Int8FlatIndex:
+    """Maximum-inner-product index over int8 scalar-quantised rows on one GPU (faiss IndexScalarQuantizer QT_8bit with one
+    range per row; sentence-transformers "int8"): d bytes + one fp32 scale per vector where FlatIPIndex keeps 2 d bytes.  Same
+    surface as FlatIPIndex / BinaryFlatIndex.  The score of a pair is ((float)(q_codes . d_codes) * d_scale) * q_scale with an
+    exact integer dot product (cx_search_int8_topk, csrc/search.hip): queries are quantised per row as the corpus is.
+    search_int8_rescored re-scores its candidates exactly against the float rows."""
+
+    def __init__(self, d: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        _check_code_dim(d)
+        self.d = int(d)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("Int8FlatIndex runs on the GPU (cx_search_int8_topk); there is no CPU path")
+        self.workspace_bytes = int(workspace_bytes)
+        self._store: Optional[torch.Tensor] = None    # (capacity, d) int8; rows [0, ntotal) are the corpus
+        self._scale: Optional[torch.Tensor] = None    # (capacity,) fp32
+        self.ntotal = 0
+
+    def reset(self) -> None:
+        self._store = None
+        self._scale = None
+        self.ntotal = 0
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """The stored codes, (ntotal, d) int8 (a view)."""
+        if self._store is None:
+            return torch.empty(0, self.d, dtype=torch.int8, device=self.device)
+        return self._store[: self.ntotal]
+
+    @property
+    def scales(self) -> torch.Tensor:
+        """The stored scales, (ntotal,) float32 (a view)."""
+        if self._scale is None:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        return self._scale[: self.ntotal]
+
+    def reserve(self, n: int) -> None:
+        """Allocate room for n vectors in total, so that adding a corpus in chunks never copies it."""
+        if n > MAX_NTOTAL:
+            raise ValueError(f"Int8FlatIndex holds at most {MAX_NTOTAL} vectors")
+        cap = 0 if self._store is None else self._store.shape[0]
+        if n > cap:
+            grown = torch.empty(n, self.d, dtype=torch.int8, device=self.device)
+            gscale = torch.empty(n, dtype=torch.float32, device=self.device)
+            if self.ntotal:
+                grown[: self.ntotal].copy_(self._store[: self.ntotal])
+                gscale[: self.ntotal].copy_(self._scale[: self.ntotal])
+            self._store, self._scale = grown, gscale
+
+    def _check_pair(self, pair):
+        """A (codes int8 (n, d), scales float32 (n,)) tuple -> host-or-device tensors, shapes and dtypes checked."""
+        c, s = (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t)) for t in pair)
+        if c.dtype != torch.int8 or c.dim() != 2 or c.shape[1] != self.d:
+            raise ValueError(f"expected (n, {self.d}) int8 codes, got {tuple(c.shape)} {c.dtype}")
+        if s.dtype != torch.float32 or s.dim() != 1 or s.shape[0] != c.shape[0]:
+            raise ValueError(f"expected ({c.shape[0]},) float32 scales, got {tuple(s.shape)} {s.dtype}")
+        return c, s
+
+    def _check_rows(self, x) -> int:
+        if len(np.shape(x)) != 2 or np.shape(x)[1] != self.d:
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(x))}")
+        return int(np.shape(x)[0])
+
+    def _quantize_into(self, x, codes: torch.Tensor, scales: torch.Tensor) -> None:
+        """Float rows x (a tensor anywhere, an array or a memmap) -> the given device views, QUANTIZE_ROWS rows at a time: a host
+        source is never on the device as a whole."""
+        n = codes.shape[0]
+        for r0 in range(0, n, QUANTIZE_ROWS):
+            r1 = min(n, r0 + QUANTIZE_ROWS)
+            part = x[r0:r1]
+            if not isinstance(part, torch.Tensor):
+                part = np.asarray(part)
+                part = np.ascontiguousarray(part if part.dtype == np.float32 else part.astype(np.float32))
+                part = torch.from_numpy(part if part.flags.writeable else part.copy())   # (a read-only memmap slice)
+            _quantize_rows_device(_quantizable(part.to(self.device)), codes[r0:r1], scales[r0:r1])
+
+    def add(self, x) -> None:
+        """Append rows: float vectors are quantised per row on the device (quantize_rows_int8's contract), a
+        (codes int8 (n, d), scales float32 (n,)) tuple is taken as it is."""
+        if _is_code_pair(x):
+            c, s = self._check_pair(x)
+            n = c.shape[0]
+            self.reserve(self.ntotal + n)
+            self._store[self.ntotal: self.ntotal + n].copy_(c)
+            self._scale[self.ntotal: self.ntotal + n].copy_(s)
+        else:
+            n = self._check_rows(x)
+            self.reserve(self.ntotal + n)
+            self._quantize_into(x, self._store[self.ntotal: self.ntotal + n], self._scale[self.ntotal: self.ntotal + n])
+        self.ntotal += n
+
+    def batch_rows(self, M: int, k: int) -> int:
+        """The largest query batch (all of M, else halved down to a multiple of 128) whose workspace fits the bound."""
+        h = _C.lib()
+        m = M
+        while m > 128 and h.cx_search_int8_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
+            m = max(128, (m // 2) // 128 * 128)
+        return m
+
+    def _query_codes(self, queries):
+        """float rows or a (codes, scales) tuple -> (codes (M, d) int8, scales (M,) fp32) on the index's device."""
+        if _is_code_pair(queries):
+            c, s = self._check_pair(queries)
+            return c.to(self.device).contiguous(), s.to(self.device).contiguous()
+        M = self._check_rows(queries)
+        qc = torch.empty(M, self.d, dtype=torch.int8, device=self.device)
+        qs = torch.empty(M, dtype=torch.float32, device=self.device)
+        self._quantize_into(queries, qc, qs)
+        return qc, qs
+
+    def search(self, queries, k: int, exclude=None, below=None, nsplit: int = 0):
+        """-> (scores (M, k) float32, ids (M, k) int64): per query the k largest int8 scores, descending, ties to the lower id;
+        missing entries are (-inf, -1).  queries: float rows (quantised per row) or a (codes, scales) tuple, as for add.
+        exclude, below (a strict bound on the int8 score), nsplit: as FlatIPIndex.search.  numpy in -> numpy out, torch in ->
+        torch out on the index's device."""
+        first = queries[0] if _is_code_pair(queries) else queries
+        as_numpy = not isinstance(first, torch.Tensor)
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        if _is_code_pair(queries):
+            M = self._check_pair(queries)[0].shape[0]
+        else:
+            M = self._check_rows(queries)
+        xptr, xids = _exclusion_csr_host(exclude, M)
+        bel = None
+        if below is not None:
+            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
+            if bel.numel() != M:
+                raise ValueError(f"below has {bel.numel()} entries for {M} queries")
+            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        qc, qs = self._query_codes(queries)
+        if xptr is not None:
+            xptr = xptr.to(self.device)
+            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
+        scores = torch.empty(M, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
+        if M:
+            h = _C.lib()
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                mb = self.batch_rows(M, k)
+                ws = None
+                if self.ntotal:
+                    last = M - (M - 1) // mb * mb
+                    nbytes = max(h.cx_search_int8_ws_bytes(mb, self.ntotal, k, nsplit),
+                                 h.cx_search_int8_ws_bytes(last, self.ntotal, k, nsplit))
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                D, ds = self.codes, self.scales
+                for b0 in range(0, M, mb):
+                    m = min(mb, M - b0)
+                    _C.check(h.cx_search_int8_topk(qc[b0].data_ptr(), D.data_ptr() if self.ntotal else None,
+                                                   qs[b0:].data_ptr(), ds.data_ptr() if self.ntotal else None, m, self.ntotal,
+                                                   self.d, self.d, self.d, k,
+                                                   None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
+                                                   None if bel is None else bel[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
+                                                   scores[b0].data_ptr(), ids[b0].data_ptr(), stream), "cx_search_int8_topk")
+        if as_numpy:
+            return scores.cpu().numpy(), ids.cpu().numpy()
+        return scores, ids
+
+
+def search_int8_rescored(index: Int8FlatIndex, vectors, queries, k: int, rescore_factor: int = 2, exclude=None, below=None):
+    """Coarse int8 search + exact re-scoring: the min(k * rescore_factor, 4096) best int8 scores of `index` per query, then the
+    k best of those by exact inner product with `vectors` (the corpus the codes were made from: device bf16 rows, a host array
+    or a memmap; see rescore).  queries: float rows.  exclude applies to the coarse stage, below to the exact score.
+    -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit when the candidate lists cover the corpus.  Lists longer
+    than the kernel's k bound (1024) are fetched in pages (_paged_candidates)."""
+    k = int(k)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    as_numpy = not isinstance(queries, torch.Tensor)
+    M = index._check_rows(queries)
+    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
+    if below is not None and int(np.size(below)) != M:
+        raise ValueError(f"below has {int(np.size(below))} entries for {M} queries")
+    qd = _to_device_2d(queries, index.d, index.device)
+    qc = index._query_codes(queries)
+    cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
 
 
 def encode(model, texts: Sequence[str], tokenizer, batch_size: int = 256, max_length: int = 512,

@@ -82,7 +82,8 @@ def load_tower(checkpoint, device: str):
 
 
 COARSE = ("exact", "binary")
-ADD_ROWS = 1 << 18   # binary: document rows binarised per upload
+STORAGE = ("bf16", "int8")
+ADD_ROWS = 1 << 18   # binary / int8: document rows encoded per upload
 
 
 def add_search_arguments(ap) -> None:
@@ -91,7 +92,11 @@ def add_search_arguments(ap) -> None:
                          "sign codes (1/16 of the memory), then exact re-scoring of k * rescore_factor candidates against "
                          "the memory-mapped document .npy")
     ap.add_argument("--rescore_factor", type=int, default=4,
-                    help="binary: candidates re-scored per returned neighbour (k * rescore_factor, at most 4096)")
+                    help="binary / int8: candidates re-scored per returned neighbour (k * rescore_factor, at most 4096)")
+    ap.add_argument("--storage", choices=STORAGE, default="bf16",
+                    help="bf16: the corpus on the device as bf16 rows; int8: as int8 codes + one fp32 scale per row (half the "
+                         "memory), searched by int8 score, then exact re-scoring of k * rescore_factor candidates against the "
+                         "memory-mapped document .npy (with --coarse exact, without --ivf_lists)")
     ap.add_argument("--ivf_lists", type=int, default=0,
                     help="exact: search inside K k-means lists of the corpus instead of all of it (IVFFlatIndex); 0 = off")
     ap.add_argument("--ivf_nprobe", type=int, default=None,
@@ -103,6 +108,11 @@ def add_search_arguments(ap) -> None:
 
 def check_search_arguments(ap, args) -> dict:
     """Refuse flag combinations the search cannot serve (ap.error) -> the ivf_* keyword arguments of search()."""
+    if getattr(args, "storage", "bf16") == "int8":
+        if args.coarse != "exact":
+            ap.error("--storage int8 goes with --coarse exact only")
+        if args.ivf_lists:
+            ap.error("--storage int8 does not go with --ivf_lists")
     if args.ivf_lists < 0:
         ap.error("--ivf_lists must not be negative")
     if args.ivf_lists == 0:
@@ -122,21 +132,36 @@ def check_search_arguments(ap, args) -> dict:
 
 def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, coarse: str = "exact",
            rescore_factor: int = 4, ivf_lists: int = 0, ivf_nprobe: Optional[int] = None, ivf_centroids=None,
-           ivf_sample: Optional[int] = None, ivf_iters: int = 25):
+           ivf_sample: Optional[int] = None, ivf_iters: int = 25, storage: str = "bf16"):
     """-> (scores, ids) numpy.  coarse="exact": exact inner-product top-k over the bf16 corpus (FlatIPIndex).
     coarse="binary": Hamming top-(k * rescore_factor) over sign codes (BinaryFlatIndex), re-scored exactly against doc_emb,
     which stays on the host (an array or a memmap); equal to "exact" once the candidates cover the corpus.
     ivf_lists = K > 0 (with "exact"): the top-k of the ivf_nprobe (default min(8, K)) nearest of K k-means lists
     (IVFFlatIndex; centroids fitted to doc_emb with ivf_iters iterations on ivf_sample rows, or read from the .npy path /
-    array ivf_centroids); equal to "exact" when every list is probed."""
+    array ivf_centroids); equal to "exact" when every list is probed.
+    storage="int8" (with "exact", without ivf_lists): int8 top-(k * rescore_factor) over per-row quantised codes
+    (Int8FlatIndex), re-scored exactly against doc_emb, which stays on the host; equal to "bf16" once the candidates cover the
+    corpus."""
     import torch
 
-    from ..search import BinaryFlatIndex, FlatIPIndex, IVFFlatIndex, search_binary_rescored
+    from ..search import BinaryFlatIndex, FlatIPIndex, Int8FlatIndex, IVFFlatIndex, search_binary_rescored, search_int8_rescored
 
     if coarse not in COARSE:
         raise ValueError(f"coarse must be one of {COARSE}, got {coarse!r}")
+    if storage not in STORAGE:
+        raise ValueError(f"storage must be one of {STORAGE}, got {storage!r}")
     if ivf_lists and coarse != "exact":
         raise ValueError("ivf_lists goes with coarse='exact' only")
+    if storage == "int8" and (coarse != "exact" or ivf_lists):
+        raise ValueError("storage='int8' goes with coarse='exact' and without ivf_lists only")
+    if storage == "int8":
+        n, d = np.shape(doc_emb)
+        index = Int8FlatIndex(d, device=device)
+        index.reserve(n)
+        for r0 in range(0, n, ADD_ROWS):
+            index.add(np.asarray(doc_emb[r0: r0 + ADD_ROWS], dtype=np.float32))
+        return search_int8_rescored(index, doc_emb, np.asarray(query_emb, dtype=np.float32), k, rescore_factor,
+                                    exclude=exclude, below=below)
     if coarse == "binary":
         n, d = np.shape(doc_emb)
         index = BinaryFlatIndex(d, device=device)

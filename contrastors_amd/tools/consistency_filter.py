@@ -31,11 +31,11 @@ def keep_ids(ids: List, top_k_indices) -> List:
 
 
 def filter_pairs(ids: List, q_emb, d_emb, device: str = "cuda", k: int = 2, coarse: str = "exact",
-                 rescore_factor: int = 4, **ivf) -> List:
+                 rescore_factor: int = 4, storage: str = "bf16", **ivf) -> List:
     """ids[i] names pair i; -> the kept ids, in ascending id order.  ivf: the ivf_* arguments of _common.search."""
     pos = sorted(range(len(ids)), key=lambda i: ids[i])
     _, top = search(np.asarray(d_emb)[pos], np.asarray(q_emb)[pos], k, device, coarse=coarse, rescore_factor=rescore_factor,
-                    **ivf)
+                    storage=storage, **ivf)
     return keep_ids(ids, top)
 
 
@@ -81,7 +81,7 @@ def main(argv=None) -> int:
     if args.query_embeddings:
         q = np.load(args.query_embeddings)
         n = q.shape[0]
-        d = load_npy(args.document_embeddings, n, "document", mmap=args.coarse == "binary")
+        d = load_npy(args.document_embeddings, n, "document", mmap=args.coarse == "binary" or args.storage == "int8")
         ids = json.loads(Path(args.ids).read_text()) if args.ids else list(range(n))
         if len(ids) != n:
             ap.error(f"--ids has {len(ids)} entries for {n} pairs")
@@ -96,7 +96,7 @@ def main(argv=None) -> int:
                          args.max_length, args.device).cpu().numpy()
     if len(set(ids)) != len(ids):
         ap.error("pair ids must be unique")
-    kept = filter_pairs(ids, q, d, args.device, args.k, args.coarse, args.rescore_factor, **ivf)
+    kept = filter_pairs(ids, q, d, args.device, args.k, args.coarse, args.rescore_factor, storage=args.storage, **ivf)
     out = Path(args.output_dir)
     out.mkdir(parents=True, exist_ok=True)
     n_existing = len(list(out.glob("ids_to_keep_*.json")))

@@ -208,7 +208,7 @@ def _embeddings(args, q_texts, d_texts):
         raise SystemExit("error: give both --query_embeddings and --document_embeddings, or neither")
     if args.query_embeddings:
         return (load_npy(args.query_embeddings, len(q_texts), "query"),
-                load_npy(args.document_embeddings, len(d_texts), "document", mmap=args.coarse == "binary"))
+                load_npy(args.document_embeddings, len(d_texts), "document", mmap=args.coarse == "binary" or args.storage == "int8"))
     q = encode_texts(q_texts, args.model, args.tokenizer, args.batch_size, args.max_length, args.device, args.query_prefix)
     d = encode_texts(d_texts, args.model, args.tokenizer, args.batch_size, args.max_length, args.device,
                      args.document_prefix)
@@ -242,7 +242,8 @@ def main(argv=None) -> int:
     if topk:
         queries, documents, records = load_records(args.dataset, args.query_key, args.document_key, args.negatives_key)
         q_emb, d_emb = _embeddings(args, queries, documents)
-        _, indices = search(d_emb, q_emb, args.k, args.device, coarse=args.coarse, rescore_factor=args.rescore_factor, **ivf)
+        _, indices = search(d_emb, q_emb, args.k, args.device, coarse=args.coarse, rescore_factor=args.rescore_factor,
+                            storage=args.storage, **ivf)
         records = select_topk(records, documents, indices, args.k, args.query_key, args.document_key,
                               args.negatives_key, np.random.RandomState(args.seed))
         write_shards(records, args.output_dir, meta)
@@ -259,12 +260,12 @@ def main(argv=None) -> int:
         if missing:
             ap.error(f"--query_ids lacks {len(missing)} queries of the qrels split, e.g. {missing[0]!r}")
         q_emb = q_all[[where[qid] for qid in queries]]
-        d_emb = load_npy(args.document_embeddings, len(documents), "document", mmap=args.coarse == "binary")
+        d_emb = load_npy(args.document_embeddings, len(documents), "document", mmap=args.coarse == "binary" or args.storage == "int8")
     else:
         q_emb, d_emb = _embeddings(args, list(queries.values()), documents)
     pairs, rows, excl, below = margin_pairs(qrels, qid2index, docid2index, q_emb, d_emb, args.margin)
     _, indices = search(d_emb, np.asarray(q_emb)[rows], args.max_negatives, args.device, exclude=excl, below=below,
-                        coarse=args.coarse, rescore_factor=args.rescore_factor, **ivf)
+                        coarse=args.coarse, rescore_factor=args.rescore_factor, storage=args.storage, **ivf)
     mined, dropped = select_margin(pairs, indices, corpus, queries, documents, args.k, args.query_key,
                                    args.document_key, args.negatives_key)
     random.Random(args.seed).shuffle(mined)

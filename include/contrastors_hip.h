@@ -509,6 +509,26 @@ int cx_search_hamming_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, 
 int cx_rescore_topk(const uint16_t* Q, const uint16_t* D, const int64_t* cand, const int64_t* ids, int M, long R, int d,
                     long ldq, long ldd, int c, int k, const float* below, float* out_scores, int64_t* out_ids,
                     void* stream);
+/* ---- int8 scalar-quantised index (sentence-transformers "int8", faiss SQ8 with one range per row; csrc/quantize_int8.hip,
+ *          csrc/search.hip).  Additive: cx_abi_version stays 10. ------------------------------------------------------------
+ * cx_quantize_rows_int8: X:(rows,d) with leading dimension ldx ELEMENTS, dtype 0 = fp32, 1 = bf16 (cx_pack_sign_bits'
+ * operands; X aligned to its element).  out:(rows,d) int8, leading dimension ldo BYTES % 16 == 0, 16-B aligned; scale:(rows)
+ * fp32.  Per row: amax = max_j |x_j| in fp32; amax < 2^-100: codes 0, scale 0; otherwise inv = 127.0f / amax,
+ * scale = amax / 127.0f (IEEE divisions), code_j = clamp(rint(x_j * inv), -127, 127) (fp32 product, half to even; never -128).
+ * Non-finite input is never an out-of-bounds access; NaN elements are skipped by the maximum and get code -127, an infinite
+ * element makes the row's scale inf (finite elements 0, infinite ones -127).  d % 64 == 0, 64 <= d <= 1024. */
+int cx_quantize_rows_int8(const void* X, int dtype, long rows, int d, long ldx, int8_t* out, long ldo, float* scale,
+                          void* stream);
+/* Top-k over such codes, cx_search_topk argument for argument with these differences: Q:(M,d) ldq and D:(N,d) ldd int8, leading
+ * dimensions in BYTES, each >= d and % 16 == 0, pointers 16-B aligned (CX_ERR_ALIGN); q_scale:(M) and d_scale:(N) fp32.
+ * The score of (m, n):  acc = sum_j Q[m][j] D[n][j] (int32, exact: v_mfma_i32_16x16x64_i8; |acc| <= 127^2 * 1024 < 2^24),
+ * s = ((float)acc * d_scale[n]) * q_scale[m] -- two fp32 multiplications in that order, no FMA.  k, the exclusion CSR, below
+ * (a strict upper bound on s), nsplit (no effect on the result), the order (s descending, id ascending), the (-inf, -1) padding,
+ * the error codes, N == 0 and M == 0: as cx_search_topk.  ws: 16-B aligned, cx_search_int8_ws_bytes(M, N, k, nsplit) bytes. */
+long cx_search_int8_ws_bytes(int M, long N, int k, int nsplit);
+int cx_search_int8_topk(const int8_t* Q, const int8_t* D, const float* q_scale, const float* d_scale, int M, long N, int d,
+                        long ldq, long ldd, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
+                        int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream);
 /* backward of  coef * sum_i loss_rows[i]:  Gm[i][j] = coef*scale*(softmax_ij - [j==label_i]) is written to
  * Gmat:(N,G) and GmatT:(G,N) fp32 scratch; dQ:(N,dim) = Gm D, dD:(G,dim) = Gm^T Q (overwritten);
  * dscale_accum (may be NULL): += coef * sum_ij (softmax_ij - y_ij) * (Q D^T)_ij   (d loss / d scale).
