@@ -24,8 +24,9 @@
 // id arrays as the search entry points write them; ids may be mapped on the way out (list positions -> original ids).
 //
 // cx_search_int8_topk is stage 1 over int8 codes with one fp32 scale per row (search_int8_tiles_kernel, below the bf16 kernel):
-// its own operand staging, K loop (v_mfma_i32_16x16x64_i8) and scaling epilogue; Cand, SearchLds, insert_row<false>,
-// merge_lists_kernel<SplitLists> and auto_splits are shared as they are.
+// its own operand staging, K loop (v_mfma_i32_16x16x64_i8) and scaling epilogue; Cand, SearchLds, insert_row<WIN>,
+// merge_lists_kernel<SplitLists> and auto_splits are shared as they are.  cx_search_int8_window_topk is that kernel with
+// WIN = true, the way cx_search_window_topk is search_tiles_kernel<true>: the scan of an IVF index over int8 codes.
 #include <type_traits>
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
@@ -172,16 +173,10 @@ CX_DEVICE void insert_row(const SearchParams& p, SearchLdsT<WIN>& L, const float
     wave_sync();
 }
 
-template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
-    extern __shared__ __attribute__((aligned(16))) char dsm[];
-    SearchLdsT<WIN>& L = *reinterpret_cast<SearchLdsT<WIN>*>(dsm);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
-    const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
-    const int m0 = tm * TM;
-    int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
-    const int nk = p.d / BK;
-
+// Every row's threshold, bound, count and flag and, with WIN, its clamped window; t_begin / t_end become the band [t0, t1) of
+// the tile's non-empty windows (WIN = false: the split's range stays).  Ends behind a workgroup barrier.
+template <bool WIN>
+CX_DEVICE void init_rows(const SearchParams& p, SearchLdsT<WIN>& L, int m0, int tid, int& t_begin, int& t_end) {
     if constexpr (WIN) {
         if (tid == 0) { L.minmid = 0x7fffffff; L.maxend = 0; }
         __syncthreads();
@@ -218,6 +213,19 @@ template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kerne
         t_begin = L.maxend > 0 ? (L.minmid + 1) / TN : 0;
         t_end = L.maxend > 0 ? (L.maxend + TN - 1) / TN : 0;
     }
+}
+
+template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    SearchLdsT<WIN>& L = *reinterpret_cast<SearchLdsT<WIN>*>(dsm);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
+    const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
+    const int m0 = tm * TM;
+    int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
+    const int nk = p.d / BK;
+
+    init_rows<WIN>(p, L, m0, tid, t_begin, t_end);
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * TN;
@@ -322,7 +330,7 @@ struct Int8Params : SearchParams {   // (Q, D of the base stay null; ldq / ldd c
     const float* d_scale;  // (N)
 };
 
-struct Int8SearchLds : SearchLds {
+template <bool WIN> struct Int8SearchLds : SearchLdsT<WIN> {
     alignas(16) float dsc[TN];    // the scales of the current corpus tile's rows (read four at a time)
     float qsc[TM];                // ... and of the query tile's rows
 };
@@ -339,26 +347,20 @@ CX_DEVICE void stage8(const Int8Params& p, int m0, int n0, int k0, int tid, uint
     }
 }
 
-__global__ __launch_bounds__(256, 1) void search_int8_tiles_kernel(Int8Params p) {
+// WIN = true: the id window of search_tiles_kernel<true>, tested in the same places, and the same band walk [t0, t1) in one
+// piece; dsc is loaded from the scales of corpus tile t itself, wherever the band starts.
+template <bool WIN> __global__ __launch_bounds__(256, 1) void search_int8_tiles_kernel(Int8Params p) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
-    Int8SearchLds& L = *reinterpret_cast<Int8SearchLds*>(dsm);
+    Int8SearchLds<WIN>& L = *reinterpret_cast<Int8SearchLds<WIN>*>(dsm);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
     const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
     const int m0 = tm * TM;
-    const int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
+    int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
     const int nk = (p.d + BK8 - 1) / BK8;
 
-    if (tid < TM) {
-        const int m = m0 + tid;
-        L.thr[tid] = m < p.M ? -INFINITY : INFINITY;   // rows past M never pass the threshold test
-        L.bel[tid] = (m < p.M && p.below) ? p.below[m] : INFINITY;
-        L.qsc[tid] = p.q_scale[min(m, p.M - 1)];
-        L.cnt[tid] = 0;
-        L.flag[tid] = 0;
-    }
-    if (tid == 0) L.any = 0;
-    __syncthreads();
+    if (tid < TM) L.qsc[tid] = p.q_scale[min(m0 + tid, p.M - 1)];   // (read in the epilogue, behind init_rows' barrier)
+    init_rows<WIN>(p, L, m0, tid, t_begin, t_end);
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * TN;
@@ -403,6 +405,12 @@ __global__ __launch_bounds__(256, 1) void search_int8_tiles_kernel(Int8Params p)
             const int row = wq * 64 + a * 16 + l15;
             const float thr = L.thr[row], bel = L.bel[row], qs = L.qsc[row];
             bool h = false;
+            int lim = 0, top = 0;   // WIN: column nb + c is inside the window  <=>  lim < c < top
+            if constexpr (WIN) {
+                const int nb = n0 + wd * 64 + 4 * lh;
+                lim = L.mid[row] - nb;
+                top = L.end[row] - nb;
+            }
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const f32x4_t ds = *reinterpret_cast<const f32x4_t*>(&L.dsc[wd * 64 + b * 16 + 4 * lh]);
@@ -410,7 +418,8 @@ __global__ __launch_bounds__(256, 1) void search_int8_tiles_kernel(Int8Params p)
                 for (int r = 0; r < 4; ++r) {
                     const float v = __fmul_rn(__fmul_rn((float)acc[a][b][r], ds[r]), qs);
                     sc[a][b][r] = v;
-                    h |= (v > thr) & (v < bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
+                    if constexpr (WIN) h |= (v > thr) & (v < bel) & (b * 16 + r > lim) & (b * 16 + r < top);   // (end <= N)
+                    else h |= (v > thr) & (v < bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
                 }
             }
             if (h) L.flag[row] = 1;
@@ -427,7 +436,7 @@ __global__ __launch_bounds__(256, 1) void search_int8_tiles_kernel(Int8Params p)
                     *reinterpret_cast<f32x4_t*>(tile + (wq * 64 + a * 16 + l15) * TN + wd * 64 + b * 16 + 4 * lh) = sc[a][b];
             __syncthreads();
             for (int row = wave; row < TM; row += 4)
-                if (L.flag[row]) insert_row<false>(p, L, tile, row, m0 + row, n0, split, wave, lane);
+                if (L.flag[row]) insert_row<WIN>(p, L, tile, row, m0 + row, n0, split, wave, lane);
             __syncthreads();
             if (tid < TM) L.flag[tid] = 0;
             if (tid == 0) L.any = 0;
@@ -613,8 +622,9 @@ int cx_search_int8_topk(const int8_t* Q, const int8_t* D, const float* q_scale, 
         p.lists = lists; p.counts = counts;
         const int tiles_m = (M + TM - 1) / TM;
         static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel), (int)sizeof(Int8SearchLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_int8_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(Int8SearchLds), s, p);
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel<false>), (int)sizeof(Int8SearchLds<false>)))
+            return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_int8_tiles_kernel<false>, dim3(tiles_m * ns), dim3(256), sizeof(Int8SearchLds<false>), s, p);
         if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
     }
     const SplitLists S = {lists, counts, ns, k};
@@ -652,6 +662,44 @@ int cx_search_window_topk(const uint16_t* Q, const uint16_t* D, int M, long N, i
         static CxLdsOptIn opt;
         if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel<true>), (int)sizeof(WinSearchLds))) return CX_ERR_LAUNCH;
         hipLaunchKernelGGL(search_tiles_kernel<true>, dim3((M + TM - 1) / TM), dim3(256), sizeof(WinSearchLds), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    // the row's one list, padded, in the output layout
+    const SplitLists S = {lists, counts, 1, k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? 1 : 0, k, out_scores,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_search_int8_window_ws_bytes(int M, int k) { return cx_search_window_ws_bytes(M, k); }
+
+int cx_search_int8_window_topk(const int8_t* Q, const int8_t* D, const float* q_scale, const float* d_scale, int M, long N,
+                               int d, long ldq, long ldd, int k, const int64_t* min_id, const int64_t* end_id,
+                               const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
+                               float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Q || !q_scale || !out_scores || !out_ids || (N > 0 && (!D || !d_scale || !ws)) || (excl_ptr && !excl_ids))
+        return CX_ERR_ARG;
+    if (ldq < d || (ldq % 16) != 0 || (N > 0 && (ldd < d || (ldd % 16) != 0))) return CX_ERR_ALIGN;
+    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    Cand* lists = reinterpret_cast<Cand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
+    if (N > 0) {
+        Int8Params p = {};
+        p.Q8 = Q; p.D8 = D; p.q_scale = q_scale; p.d_scale = d_scale; p.ldq = ldq; p.ldd = ldd;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = 1;   // one workgroup walks a query tile's whole band
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = p.tiles_n;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
+        p.min_id = min_id; p.end_id = end_id;
+        p.lists = lists; p.counts = counts;
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel<true>), (int)sizeof(Int8SearchLds<true>)))
+            return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_int8_tiles_kernel<true>, dim3((M + TM - 1) / TM), dim3(256), sizeof(Int8SearchLds<true>), s, p);
         if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
     }
     // the row's one list, padded, in the output layout

@@ -21,6 +21,9 @@ which may stay on the host or in a memory-mapped file (csrc/search_binary.hip).
 (`quantize_rows_int8`, csrc/quantize_int8.hip), searched with an exact integer dot product on the matrix cores
 (cx_search_int8_topk, csrc/search.hip); `search_int8_rescored` re-scores its candidates exactly like the binary pipeline.
 
+`IVFInt8Index` is both at once (faiss `IndexIVFScalarQuantizer`, QT_8bit): IVFFlatIndex's lists over Int8FlatIndex's codes,
+scanned by the windowed int8 kernel (cx_search_int8_window_topk); `search_ivf_int8_rescored` is its two-stage form.
+
 `encode` is the embedding side: this project's BiEncoder under no_grad, length-sorted batches, results in input order.
 """
 from __future__ import annotations
@@ -464,22 +467,16 @@ def ivf_pair_exclusions(row_ptr: torch.Tensor, ids: torch.Tensor, pair_query: to
     return pair_ptr, torch.where(ok, pos, torch.full_like(x, -1))
 
 
-class IVFFlatIndex:
-    """Inverted-file index with uncompressed bf16 rows on one GPU (faiss IndexIVFFlat, inner product): a coarse quantiser of
-    nlist centroids, every stored row in the list of its best centroid, and a search that scores only the rows of the nprobe
-    lists whose centroids are nearest to the query.  Scores have the bits FlatIPIndex.search gives the pair, so probing every
-    list returns exactly its result.
+class _IVFLists:
+    """The list bookkeeping of the inverted-file indexes: the coarse quantiser, labelling, the pending chunks, the stable sort
+    by label, the pair plan of a search and the merge.  A subclass supplies what is stored per row (a tuple of tensors per chunk,
+    kept in self._cols in list order), how many bytes a gathered pair row takes (_pair_row_bytes), how queries are taken
+    (_check_queries / _prepare_queries) and which kernel entry scans the pair rows (_ENTRY, _scan)."""
 
-    The rows are kept sorted by list (a stable sort: a list is a run of ascending original ids); a search sorts its
-    (query, probed list) pairs by list too and ONE windowed top-k launch per batch (cx_search_window_topk) walks, for every
-    128-pair tile, only the corpus tiles of the lists that tile probes; cx_topk_merge_lists merges each query's nprobe lists
-    and maps positions back to original ids.  No per-list launches; nothing but sizes is read back.
-
-    The sort happens at the first search after an add and needs, at its peak, twice the corpus in device memory (the old
-    rows and their gathered copy).  Not here: L2, residual / PQ codes, host rows, save / load (centroids go in and out as
-    arrays), incremental adds without a re-sort."""
+    _ENTRY = ""                      # the windowed top-k entry point of the list scan
 
     def __init__(self, d: int, nlist: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
+        name = type(self).__name__
         if d % 64 or not 64 <= d <= 1024:
             raise ValueError(f"d must be a multiple of 64 in [64, 1024], got {d}")
         if not 1 <= int(nlist) <= MAX_NTOTAL:
@@ -487,7 +484,7 @@ class IVFFlatIndex:
         self.d, self.nlist = int(d), int(nlist)
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("IVFFlatIndex runs on the GPU (cx_search_window_topk); there is no CPU path")
+            raise RuntimeError(f"{name} runs on the GPU ({self._ENTRY}); there is no CPU path")
         self.workspace_bytes = int(workspace_bytes)
         self.seed = int(seed)
         self._centroids: Optional[torch.Tensor] = None    # (nlist, d) fp32
@@ -496,12 +493,12 @@ class IVFFlatIndex:
 
     def reset(self) -> None:
         """Drop the stored rows; the centroids stay."""
-        self._rows: Optional[torch.Tensor] = None         # (n sorted, d) bf16 in list order
+        self._cols: Optional[tuple] = None                # what is stored per row, (n sorted, ...) tensors in list order
         self._order: Optional[torch.Tensor] = None        # (n sorted) int64: original id of every sorted position
         self._inv: Optional[torch.Tensor] = None          # (n sorted) int64: its inverse
         self._labels: Optional[torch.Tensor] = None       # (n sorted) int32, ascending
         self._list_ptr: Optional[torch.Tensor] = None     # (nlist + 1) int64
-        self._pending = []                                # (rows, labels) chunks added since the last sort
+        self._pending = []                                # (per-row tensors, labels) chunks added since the last sort
         self.ntotal = 0
 
     @property
@@ -516,7 +513,7 @@ class IVFFlatIndex:
 
     def _require_trained(self) -> None:
         if self._centroids is None:
-            raise RuntimeError("IVFFlatIndex has no centroids yet: call train() first")
+            raise RuntimeError(f"{type(self).__name__} has no centroids yet: call train() first")
 
     def train(self, x=None, max_iter: int = 25, sample: Optional[int] = None, centroids=None) -> None:
         """Fit the nlist centroids to x (n >= nlist rows) with spherical k-means (contrastors_amd.cluster.KMeans, seeded: the
@@ -538,48 +535,45 @@ class IVFFlatIndex:
         self._coarse = FlatIPIndex(self.d, device=self.device, workspace_bytes=self.workspace_bytes)
         self._coarse.add(c)
 
-    def add(self, x) -> None:
-        """Append rows (rounded to bf16 as FlatIPIndex.add rounds); row i of the n-th add gets id ntotal + i.  Every row is
+    def _append(self, cols: tuple, xb: torch.Tensor) -> None:
+        """One chunk of rows: cols is what the index keeps of them, xb (n, d) their bf16 roundings on the device.  Every row is
         labelled with the list of its largest inner product over the centroids' bf16 roundings, ties to the lower list
         (cx_kmeans_assign without a bias): the first probe the coarse search returns for the same vector."""
-        self._require_trained()
-        xb = _to_device_2d(x, self.d, self.device)
-        if isinstance(x, torch.Tensor) and xb.data_ptr() == x.data_ptr():
-            xb = xb.clone()
         n = xb.shape[0]
-        if self.ntotal + n > MAX_NTOTAL:
-            raise ValueError(f"IVFFlatIndex holds at most {MAX_NTOTAL} vectors")
-        if n == 0:
-            return
         labels = torch.empty(n, dtype=torch.int32, device=self.device)
         best = torch.empty(n, dtype=torch.float32, device=self.device)
         C = self._coarse.vectors
         with torch.cuda.device(self.device):
             _C.check(_C.lib().cx_kmeans_assign(xb.data_ptr(), C.data_ptr(), None, n, self.nlist, self.d, self.d, self.d,
                                                labels.data_ptr(), best.data_ptr(), None, _C.cur_stream()), "cx_kmeans_assign")
-        self._pending.append((xb, labels))
+        self._pending.append((cols, labels))
         self.ntotal += n
 
     def _finalise(self) -> None:
         """Sort what was added since the last search into the lists.  The sorted rows and the new chunks are concatenated
         (sorted rows keep ascending ids per list and new ids are larger, so one stable sort by label restores the invariant),
-        the sources are released, and the rows are gathered into list order: twice the corpus at the peak."""
+        the sources are released, and the rows are gathered into list order: twice the stored corpus at the peak."""
         if not self._pending:
             return
         from .dedup import label_order
 
-        n_old = 0 if self._rows is None else self._rows.shape[0]
-        rows = ([self._rows] if n_old else []) + [r for r, _ in self._pending]
+        n_old = 0 if self._cols is None else self._cols[0].shape[0]
+        ncol = len(self._pending[0][0])
+        cols = [([self._cols[c]] if n_old else []) + [r[c] for r, _ in self._pending] for c in range(ncol)]
         labs = ([self._labels] if n_old else []) + [l for _, l in self._pending]
         ids = ([self._order] if n_old else []) + [torch.arange(n_old, self.ntotal, dtype=torch.int64, device=self.device)]
-        self._rows, self._pending = None, []
-        x = rows[0] if len(rows) == 1 else torch.cat(rows)
-        del rows
+        self._cols, self._pending = None, []
         lab = labs[0] if len(labs) == 1 else torch.cat(labs)
         ids = ids[0] if len(ids) == 1 else torch.cat(ids)
         perm = torch.from_numpy(label_order(lab.cpu().numpy())).to(self.device)
-        self._rows = x[perm]
-        del x
+        out = []
+        for c in range(ncol):
+            parts, cols[c] = cols[c], None
+            x = parts[0] if len(parts) == 1 else torch.cat(parts)
+            del parts
+            out.append(x[perm])
+            del x
+        self._cols = tuple(out)
         self._labels = lab[perm]
         self._order = ids[perm]
         self._inv = torch.empty_like(self._order)
@@ -596,20 +590,34 @@ class IVFFlatIndex:
         self._finalise()
         return self._list_ptr[1:] - self._list_ptr[:-1]
 
+    def _pair_row_bytes(self) -> int:
+        """Bytes of one gathered query as the scan takes it."""
+        raise NotImplementedError
+
     def batch_queries(self, M: int, k: int, nprobe: int) -> int:
         """Queries per launch: their nprobe pair rows each hold a gathered query, a (k) list in the kernel's workspace and one
         in the merge's input; as many (all of M, else a multiple of 128, at least one) as fit workspace_bytes."""
-        per_pair = k * 12 + k * 8 + 4 + 2 * self.d + 32
+        per_pair = k * 12 + k * 8 + 4 + self._pair_row_bytes() + 32
         m = self.workspace_bytes // (nprobe * per_pair)
         if m >= 128:
             m = m // 128 * 128
         return max(1, min(M, m))
 
+    def _check_queries(self, queries) -> int:
+        """-> M; a wrong shape raises (host only)."""
+        if len(np.shape(queries)) != 2 or np.shape(queries)[1] != self.d:
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(queries))}")
+        return int(np.shape(queries)[0])
+
+    def _prepare_queries(self, queries):
+        """-> (the queries rounded to bf16 on the device, for the coarse probe; what _scan gathers its pair rows from)."""
+        raise NotImplementedError
+
+    def _scan(self, h, prepared, b0: int, m: int, pair_q, k: int, mid, end, pptr, pids, bg, ws, ls, li, stream) -> None:
+        """One windowed top-k launch over the pair rows of queries [b0, b0 + m): lists into (ls, li)."""
+        raise NotImplementedError
+
     def search(self, queries, k: int, nprobe: int, exclude=None, below=None):
-        """-> (scores (M, k) float32, ids (M, k) int64), the conventions of FlatIPIndex.search (descending score, ties to the
-        lower id, (-inf, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows of
-        the nprobe lists nearest to each query, 1 <= nprobe <= min(nlist, 256).  ids, and the ids of exclude, are the ids
-        add() gave.  nprobe == nlist is the exact search, bit for bit."""
         as_numpy = not isinstance(queries, torch.Tensor)
         k, nprobe = int(k), int(nprobe)
         if not 1 <= k <= MAX_K:
@@ -617,15 +625,15 @@ class IVFFlatIndex:
         if not 1 <= nprobe <= min(self.nlist, MAX_NPROBE):
             raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(self.nlist, MAX_NPROBE)}], got {nprobe}")
         self._require_trained()
-        q = _to_device_2d(queries, self.d, self.device)
-        M = q.shape[0]
+        M = self._check_queries(queries)
         row_ptr, xhost = _exclusion_csr_host(exclude, M)
         bel = None
         if below is not None:
             bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
-            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
             if bel.numel() != M:
                 raise ValueError(f"below has {bel.numel()} entries for {M} queries")
+            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        q, prepared = self._prepare_queries(queries)
         scores = torch.full((M, k), -float("inf"), dtype=torch.float32, device=self.device)
         ids = torch.full((M, k), -1, dtype=torch.int64, device=self.device)
         if M and self.ntotal:
@@ -642,7 +650,6 @@ class IVFFlatIndex:
                     m = min(mq, M - b0)
                     P = m * nprobe
                     pair_q, mid, end, src = ivf_pair_plan(probes[b0: b0 + m], self._list_ptr)
-                    qg = q[b0: b0 + m][pair_q]
                     bg = None if bel is None else bel[b0: b0 + m][pair_q]
                     pptr = pids = None
                     if dptr is not None:
@@ -652,16 +659,72 @@ class IVFFlatIndex:
                     ws = torch.empty(h.cx_search_window_ws_bytes(P, k), dtype=torch.uint8, device=self.device)
                     ls = torch.empty(P, k, dtype=torch.float32, device=self.device)
                     li = torch.empty(P, k, dtype=torch.int64, device=self.device)
-                    _C.check(h.cx_search_window_topk(qg.data_ptr(), self._rows.data_ptr(), P, self.ntotal, self.d, self.d,
-                                                     self.d, k, mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
-                                                     _C.ptr(bg), ws.data_ptr(), ls.data_ptr(), li.data_ptr(), stream),
-                             "cx_search_window_topk")
+                    self._scan(h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, ws, ls, li, stream)
                     _C.check(h.cx_topk_merge_lists(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
                                                    self._order.data_ptr(), self.ntotal, scores[b0].data_ptr(),
                                                    ids[b0].data_ptr(), stream), "cx_topk_merge_lists")
         if as_numpy:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
+
+
+class IVFFlatIndex(_IVFLists):
+    """Inverted-file index with uncompressed bf16 rows on one GPU (faiss IndexIVFFlat, inner product): a coarse quantiser of
+    nlist centroids, every stored row in the list of its best centroid, and a search that scores only the rows of the nprobe
+    lists whose centroids are nearest to the query.  Scores have the bits FlatIPIndex.search gives the pair, so probing every
+    list returns exactly its result.
+
+    The rows are kept sorted by list (a stable sort: a list is a run of ascending original ids); a search sorts its
+    (query, probed list) pairs by list too and ONE windowed top-k launch per batch (cx_search_window_topk) walks, for every
+    128-pair tile, only the corpus tiles of the lists that tile probes; cx_topk_merge_lists merges each query's nprobe lists
+    and maps positions back to original ids.  No per-list launches; nothing but sizes is read back.
+
+    The sort happens at the first search after an add and needs, at its peak, twice the corpus in device memory (the old
+    rows and their gathered copy).  Not here: L2, residual / PQ codes (int8 codes with one scale per row: IVFInt8Index), host
+    rows, save / load (centroids go in and out as arrays), incremental adds without a re-sort."""
+
+    _ENTRY = "cx_search_window_topk"
+
+    @property
+    def _rows(self) -> Optional[torch.Tensor]:
+        """(n sorted, d) bf16 in list order."""
+        return None if self._cols is None else self._cols[0]
+
+    def add(self, x) -> None:
+        """Append rows (rounded to bf16 as FlatIPIndex.add rounds); row i of the n-th add gets id ntotal + i.  Every row is
+        labelled with the list of its largest inner product over the centroids' bf16 roundings, ties to the lower list
+        (cx_kmeans_assign without a bias): the first probe the coarse search returns for the same vector."""
+        self._require_trained()
+        xb = _to_device_2d(x, self.d, self.device)
+        if isinstance(x, torch.Tensor) and xb.data_ptr() == x.data_ptr():
+            xb = xb.clone()
+        n = xb.shape[0]
+        if self.ntotal + n > MAX_NTOTAL:
+            raise ValueError(f"IVFFlatIndex holds at most {MAX_NTOTAL} vectors")
+        if n == 0:
+            return
+        self._append((xb,), xb)
+
+    def _pair_row_bytes(self) -> int:
+        return 2 * self.d
+
+    def _prepare_queries(self, queries):
+        q = _to_device_2d(queries, self.d, self.device)
+        return q, q
+
+    def _scan(self, h, q, b0, m, pair_q, k, mid, end, pptr, pids, bg, ws, ls, li, stream) -> None:
+        qg = q[b0: b0 + m][pair_q]
+        _C.check(h.cx_search_window_topk(qg.data_ptr(), self._rows.data_ptr(), pair_q.numel(), self.ntotal, self.d,
+                                         self.d, self.d, k, mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
+                                         _C.ptr(bg), ws.data_ptr(), ls.data_ptr(), li.data_ptr(), stream),
+                 "cx_search_window_topk")
+
+    def search(self, queries, k: int, nprobe: int, exclude=None, below=None):
+        """-> (scores (M, k) float32, ids (M, k) int64), the conventions of FlatIPIndex.search (descending score, ties to the
+        lower id, (-inf, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows of
+        the nprobe lists nearest to each query, 1 <= nprobe <= min(nlist, 256).  ids, and the ids of exclude, are the ids
+        add() gave.  nprobe == nlist is the exact search, bit for bit."""
+        return super().search(queries, k, nprobe, exclude=exclude, below=below)
 
 
 MAX_CANDIDATES = 4096            # cx_rescore_topk's candidate-list bound
@@ -992,6 +1055,19 @@ def _quantizable(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+def _float_chunks(x, n: int, device):
+    """The n float rows of x (a tensor anywhere, an array or a memmap) as the quantiser takes them, QUANTIZE_ROWS rows at a time:
+    yields (r0, r1, rows r0 : r1 on the device, fp32 or bf16).  A host source is never on the device as a whole."""
+    for r0 in range(0, n, QUANTIZE_ROWS):
+        r1 = min(n, r0 + QUANTIZE_ROWS)
+        part = x[r0:r1]
+        if not isinstance(part, torch.Tensor):
+            part = np.asarray(part)
+            part = np.ascontiguousarray(part if part.dtype == np.float32 else part.astype(np.float32))
+            part = torch.from_numpy(part if part.flags.writeable else part.copy())   # (a read-only memmap slice)
+        yield r0, r1, _quantizable(part.to(device))
+
+
 def quantize_rows_int8(x):
     """Per-row symmetric int8 codes of the rows of x (n, d) -> (codes int8 (n, d), scales float32 (n,)), x ~ codes * scale:
     sentence-transformers' "int8" precision / faiss SQ8 with one range per row.  amax = max |x_j| in fp32; a row with
@@ -1088,15 +1164,8 @@ class Int8FlatIndex:
     def _quantize_into(self, x, codes: torch.Tensor, scales: torch.Tensor) -> None:
         """Float rows x (a tensor anywhere, an array or a memmap) -> the given device views, QUANTIZE_ROWS rows at a time: a host
         source is never on the device as a whole."""
-        n = codes.shape[0]
-        for r0 in range(0, n, QUANTIZE_ROWS):
-            r1 = min(n, r0 + QUANTIZE_ROWS)
-            part = x[r0:r1]
-            if not isinstance(part, torch.Tensor):
-                part = np.asarray(part)
-                part = np.ascontiguousarray(part if part.dtype == np.float32 else part.astype(np.float32))
-                part = torch.from_numpy(part if part.flags.writeable else part.copy())   # (a read-only memmap slice)
-            _quantize_rows_device(_quantizable(part.to(self.device)), codes[r0:r1], scales[r0:r1])
+        for r0, r1, part in _float_chunks(x, codes.shape[0], self.device):
+            _quantize_rows_device(part, codes[r0:r1], scales[r0:r1])
 
     def add(self, x) -> None:
         """Append rows: float vectors are quantised per row on the device (quantize_rows_int8's contract), a
@@ -1200,6 +1269,112 @@ def search_int8_rescored(index: Int8FlatIndex, vectors, queries, k: int, rescore
     qd = _to_device_2d(queries, index.d, index.device)
     qc = index._query_codes(queries)
     cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+
+
+class IVFInt8Index(_IVFLists):
+    """Inverted-file index over int8 scalar-quantised rows on one GPU (faiss IndexIVFScalarQuantizer, QT_8bit with one range per
+    row, inner product): IVFFlatIndex's lists -- the same centroids and rows give the same lists -- holding Int8FlatIndex's
+    codes and scales, d bytes + one fp32 scale per row.  A search probes the nprobe nearest lists with the bf16 queries, as
+    IVFFlatIndex does, and scans them with the queries quantised per row: one cx_search_int8_window_topk launch per query batch
+    over the (query, probed list) pairs, one cx_topk_merge_lists call.  Scores have the bits Int8FlatIndex.search gives the
+    pair, so probing every list returns exactly its result; search_ivf_int8_rescored re-scores the candidates exactly.
+
+    The sort happens at the first search after an add and may still peak at twice the int8 corpus in device memory (the
+    concatenated codes and their gathered copy).  Not here: adding (codes, scales, labels) made elsewhere, an in-place sort,
+    int8 re-scoring, save / load, more than one GPU."""
+
+    _ENTRY = "cx_search_int8_window_topk"
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """The stored codes in list order, (ntotal, d) int8 (a view): row p is the row add() gave the id _order[p]."""
+        self._finalise()
+        if self._cols is None:
+            return torch.empty(0, self.d, dtype=torch.int8, device=self.device)
+        return self._cols[0]
+
+    @property
+    def scales(self) -> torch.Tensor:
+        """The stored scales in list order, (ntotal,) float32 (a view)."""
+        self._finalise()
+        if self._cols is None:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        return self._cols[1]
+
+    def add(self, x) -> None:
+        """Append float rows (a tensor anywhere, an array or a memmap; codes are not taken); row i of the n-th add gets id
+        ntotal + i.  The rows go through the device QUANTIZE_ROWS at a time: each chunk is quantised per row exactly as
+        Int8FlatIndex.add quantises it, and labelled from its bf16 rounding exactly as IVFFlatIndex.add labels it; only the
+        codes, the scales and the labels stay."""
+        self._require_trained()
+        if _is_code_pair(x):
+            raise ValueError("IVFInt8Index.add takes float rows, not a (codes, scales) pair")
+        n = self._check_queries(x)
+        if self.ntotal + n > MAX_NTOTAL:
+            raise ValueError(f"IVFInt8Index holds at most {MAX_NTOTAL} vectors")
+        for r0, r1, part in _float_chunks(x, n, self.device):
+            codes = torch.empty(r1 - r0, self.d, dtype=torch.int8, device=self.device)
+            scales = torch.empty(r1 - r0, dtype=torch.float32, device=self.device)
+            _quantize_rows_device(part, codes, scales)
+            self._append((codes, scales), part.to(torch.bfloat16).contiguous())
+
+    def _pair_row_bytes(self) -> int:
+        return self.d + 4
+
+    def _prepare_queries(self, queries):
+        M = int(np.shape(queries)[0])
+        qb = torch.empty(M, self.d, dtype=torch.bfloat16, device=self.device)
+        qc = torch.empty(M, self.d, dtype=torch.int8, device=self.device)
+        qs = torch.empty(M, dtype=torch.float32, device=self.device)
+        for r0, r1, part in _float_chunks(queries, M, self.device):
+            qb[r0:r1].copy_(part)
+            _quantize_rows_device(part, qc[r0:r1], qs[r0:r1])
+        return qb, (qc, qs)
+
+    def _scan(self, h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, ws, ls, li, stream) -> None:
+        qc, qs = prepared
+        cg, sg = qc[b0: b0 + m][pair_q], qs[b0: b0 + m][pair_q]
+        D, ds = self._cols
+        _C.check(h.cx_search_int8_window_topk(cg.data_ptr(), D.data_ptr(), sg.data_ptr(), ds.data_ptr(), pair_q.numel(),
+                                              self.ntotal, self.d, self.d, self.d, k, mid.data_ptr(), end.data_ptr(),
+                                              _C.ptr(pptr), _C.ptr(pids), _C.ptr(bg), ws.data_ptr(), ls.data_ptr(),
+                                              li.data_ptr(), stream), "cx_search_int8_window_topk")
+
+    def search(self, queries, k: int, nprobe: int, exclude=None, below=None):
+        """-> (scores (M, k) float32, ids (M, k) int64), the conventions of Int8FlatIndex.search (descending int8 score, ties to
+        the lower id, (-inf, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows
+        of the nprobe lists nearest to each query, 1 <= nprobe <= min(nlist, 256).  queries: float rows, rounded to bf16 for the
+        probe over the centroids and quantised per row for the scan.  ids, and the ids of exclude, are the ids add() gave; below
+        is a strict bound on the int8 score.  nprobe == nlist is Int8FlatIndex.search, bit for bit."""
+        if _is_code_pair(queries):
+            raise ValueError("IVFInt8Index.search takes float queries, not a (codes, scales) pair")
+        return super().search(queries, k, nprobe, exclude=exclude, below=below)
+
+
+def search_ivf_int8_rescored(index: IVFInt8Index, vectors, queries, k: int, nprobe: int, rescore_factor: int = 2, exclude=None,
+                             below=None):
+    """search_int8_rescored over an IVFInt8Index: the min(k * rescore_factor, 4096) best int8 scores among the rows of the
+    nprobe lists nearest to each query, then the k best of those by exact inner product with `vectors` (the corpus the index
+    was made from, in add() order: device bf16 rows, a host array or a memmap; see rescore).  queries: float rows.  exclude
+    applies to the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit
+    when every list is probed and the candidate lists cover the corpus."""
+    k, nprobe = int(k), int(nprobe)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    if not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
+        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
+    index._require_trained()
+    as_numpy = not isinstance(queries, torch.Tensor)
+    M = index._check_queries(queries)
+    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
+    if below is not None:
+        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
+        if n_below != M:
+            raise ValueError(f"below has {n_below} entries for {M} queries")
+    qd = _to_device_2d(queries, index.d, index.device)
+    qf = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.array(queries, dtype=np.float32))
+    qf = _quantizable(qf.to(index.device))   # (once: a page of candidates quantises it again, to the same codes)
+    cand = _paged_candidates(lambda kp, ex: index.search(qf, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
     return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
 
 

@@ -83,7 +83,13 @@ def load_tower(checkpoint, device: str):
 
 COARSE = ("exact", "binary")
 STORAGE = ("bf16", "int8")
+IVF_STORAGE = ("bf16", "int8")
 ADD_ROWS = 1 << 18   # binary / int8: document rows encoded per upload
+
+
+def host_documents(args) -> bool:
+    """The searches that keep the document rows on the host: the .npy is memory-mapped, not read."""
+    return args.coarse == "binary" or args.storage == "int8" or getattr(args, "ivf_storage", "bf16") == "int8"
 
 
 def add_search_arguments(ap) -> None:
@@ -104,6 +110,10 @@ def add_search_arguments(ap) -> None:
     ap.add_argument("--ivf_centroids", default=None, help="(K, d) .npy centroid table to use instead of fitting one")
     ap.add_argument("--ivf_sample", type=int, default=None, help="fit the centroids on that many sampled documents")
     ap.add_argument("--ivf_iters", type=int, default=25, help="k-means iterations of the fit")
+    ap.add_argument("--ivf_storage", choices=IVF_STORAGE, default="bf16",
+                    help="with --ivf_lists K: bf16: the lists hold bf16 rows (IVFFlatIndex); int8: int8 codes + one fp32 scale "
+                         "per row (IVFInt8Index, half the memory), searched by int8 score, then exact re-scoring of "
+                         "k * rescore_factor candidates against the memory-mapped document .npy")
 
 
 def check_search_arguments(ap, args) -> dict:
@@ -118,6 +128,8 @@ def check_search_arguments(ap, args) -> dict:
     if args.ivf_lists == 0:
         if args.ivf_nprobe is not None or args.ivf_centroids is not None or args.ivf_sample is not None:
             ap.error("--ivf_nprobe, --ivf_centroids and --ivf_sample need --ivf_lists K")
+        if getattr(args, "ivf_storage", "bf16") != "bf16":
+            ap.error("--ivf_storage needs --ivf_lists K")
         return {}
     if args.coarse != "exact":
         ap.error("--ivf_lists goes with --coarse exact only")
@@ -126,13 +138,28 @@ def check_search_arguments(ap, args) -> dict:
         ap.error(f"--ivf_nprobe must be in [1, {min(args.ivf_lists, 256)}]")
     if args.ivf_iters < 1 or (args.ivf_sample is not None and args.ivf_sample < 1):
         ap.error("--ivf_iters and --ivf_sample must be positive")
-    return {"ivf_lists": args.ivf_lists, "ivf_nprobe": nprobe, "ivf_centroids": args.ivf_centroids,
-            "ivf_sample": args.ivf_sample, "ivf_iters": args.ivf_iters}
+    ivf = {"ivf_lists": args.ivf_lists, "ivf_nprobe": nprobe, "ivf_centroids": args.ivf_centroids,
+           "ivf_sample": args.ivf_sample, "ivf_iters": args.ivf_iters}
+    if getattr(args, "ivf_storage", "bf16") != "bf16":
+        ivf["ivf_storage"] = args.ivf_storage   # (the default adds no key)
+    return ivf
+
+
+def _fit_sample(doc_emb, sample: Optional[int], seed: int = 0):
+    """The rows KMeans.fit(doc_emb, sample=sample) fits on -- its seeded subsample, in ascending row order -- gathered on the
+    host, so that a memory-mapped corpus is not uploaded to be sampled."""
+    import torch
+
+    n = np.shape(doc_emb)[0]
+    if sample is None or int(sample) >= n:
+        return doc_emb
+    g = torch.Generator().manual_seed(seed)
+    return np.asarray(doc_emb[torch.randperm(n, generator=g)[: int(sample)].sort().values.numpy()], dtype=np.float32)
 
 
 def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, coarse: str = "exact",
            rescore_factor: int = 4, ivf_lists: int = 0, ivf_nprobe: Optional[int] = None, ivf_centroids=None,
-           ivf_sample: Optional[int] = None, ivf_iters: int = 25, storage: str = "bf16"):
+           ivf_sample: Optional[int] = None, ivf_iters: int = 25, storage: str = "bf16", ivf_storage: str = "bf16"):
     """-> (scores, ids) numpy.  coarse="exact": exact inner-product top-k over the bf16 corpus (FlatIPIndex).
     coarse="binary": Hamming top-(k * rescore_factor) over sign codes (BinaryFlatIndex), re-scored exactly against doc_emb,
     which stays on the host (an array or a memmap); equal to "exact" once the candidates cover the corpus.
@@ -141,15 +168,24 @@ def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, co
     array ivf_centroids); equal to "exact" when every list is probed.
     storage="int8" (with "exact", without ivf_lists): int8 top-(k * rescore_factor) over per-row quantised codes
     (Int8FlatIndex), re-scored exactly against doc_emb, which stays on the host; equal to "bf16" once the candidates cover the
-    corpus."""
+    corpus.
+    ivf_storage="int8" (with ivf_lists): the lists hold int8 codes (IVFInt8Index): doc_emb stays on the host and is added
+    ADD_ROWS rows at a time; the centroids are fitted on the ivf_sample rows gathered on the host (without ivf_sample: on all
+    of doc_emb, uploaded as bf16 for the fit); the int8 top-(k * rescore_factor) of the probed lists are re-scored exactly
+    against doc_emb; equal to "exact" when every list is probed and the candidates cover the corpus."""
     import torch
 
-    from ..search import BinaryFlatIndex, FlatIPIndex, Int8FlatIndex, IVFFlatIndex, search_binary_rescored, search_int8_rescored
+    from ..search import (BinaryFlatIndex, FlatIPIndex, Int8FlatIndex, IVFFlatIndex, IVFInt8Index, search_binary_rescored,
+                          search_int8_rescored, search_ivf_int8_rescored)
 
     if coarse not in COARSE:
         raise ValueError(f"coarse must be one of {COARSE}, got {coarse!r}")
     if storage not in STORAGE:
         raise ValueError(f"storage must be one of {STORAGE}, got {storage!r}")
+    if ivf_storage not in IVF_STORAGE:
+        raise ValueError(f"ivf_storage must be one of {IVF_STORAGE}, got {ivf_storage!r}")
+    if ivf_storage != "bf16" and not ivf_lists:
+        raise ValueError("ivf_storage goes with ivf_lists only")
     if ivf_lists and coarse != "exact":
         raise ValueError("ivf_lists goes with coarse='exact' only")
     if storage == "int8" and (coarse != "exact" or ivf_lists):
@@ -170,6 +206,19 @@ def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, co
             index.add(torch.as_tensor(np.asarray(doc_emb[r0: r0 + ADD_ROWS], dtype=np.float32)))
         return search_binary_rescored(index, doc_emb, np.asarray(query_emb, dtype=np.float32), k, rescore_factor,
                                       exclude=exclude, below=below)
+    if ivf_lists and ivf_storage == "int8":
+        n, d = np.shape(doc_emb)
+        index = IVFInt8Index(d, int(ivf_lists), device=device)
+        if ivf_centroids is not None:
+            table = np.load(ivf_centroids) if isinstance(ivf_centroids, (str, Path)) else ivf_centroids
+            index.train(centroids=np.asarray(table, dtype=np.float32))
+        else:
+            index.train(_fit_sample(doc_emb, ivf_sample, index.seed), max_iter=ivf_iters)
+        for r0 in range(0, n, ADD_ROWS):
+            index.add(np.asarray(doc_emb[r0: r0 + ADD_ROWS], dtype=np.float32))
+        nprobe = min(8, int(ivf_lists)) if ivf_nprobe is None else int(ivf_nprobe)
+        return search_ivf_int8_rescored(index, doc_emb, np.asarray(query_emb, dtype=np.float32), k, nprobe, rescore_factor,
+                                        exclude=exclude, below=below)
     if ivf_lists:
         docs = torch.as_tensor(np.asarray(doc_emb, dtype=np.float32))
         index = IVFFlatIndex(np.shape(doc_emb)[1], int(ivf_lists), device=device)

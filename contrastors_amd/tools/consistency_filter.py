@@ -18,7 +18,7 @@ from typing import List
 
 import numpy as np
 
-from ._common import add_search_arguments, check_search_arguments, encode_texts, load_npy, search
+from ._common import add_search_arguments, check_search_arguments, encode_texts, host_documents, load_npy, search
 
 
 def keep_ids(ids: List, top_k_indices) -> List:
@@ -81,7 +81,7 @@ def main(argv=None) -> int:
     if args.query_embeddings:
         q = np.load(args.query_embeddings)
         n = q.shape[0]
-        d = load_npy(args.document_embeddings, n, "document", mmap=args.coarse == "binary" or args.storage == "int8")
+        d = load_npy(args.document_embeddings, n, "document", mmap=host_documents(args))
         ids = json.loads(Path(args.ids).read_text()) if args.ids else list(range(n))
         if len(ids) != n:
             ap.error(f"--ids has {len(ids)} entries for {n} pairs")

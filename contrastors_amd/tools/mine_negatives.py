@@ -37,7 +37,8 @@ from typing import Dict, List
 
 import numpy as np
 
-from ._common import add_search_arguments, check_search_arguments, encode_texts, load_npy, search, triplet_metadata, write_shards
+from ._common import (add_search_arguments, check_search_arguments, encode_texts, host_documents, load_npy, search,
+                      triplet_metadata, write_shards)
 
 DEVIATIONS = """deviations from the reference scripts:
   the random fill (topk) and the record shuffle (margin) are seeded by --seed;
@@ -208,7 +209,7 @@ def _embeddings(args, q_texts, d_texts):
         raise SystemExit("error: give both --query_embeddings and --document_embeddings, or neither")
     if args.query_embeddings:
         return (load_npy(args.query_embeddings, len(q_texts), "query"),
-                load_npy(args.document_embeddings, len(d_texts), "document", mmap=args.coarse == "binary" or args.storage == "int8"))
+                load_npy(args.document_embeddings, len(d_texts), "document", mmap=host_documents(args)))
     q = encode_texts(q_texts, args.model, args.tokenizer, args.batch_size, args.max_length, args.device, args.query_prefix)
     d = encode_texts(d_texts, args.model, args.tokenizer, args.batch_size, args.max_length, args.device,
                      args.document_prefix)
@@ -260,7 +261,7 @@ def main(argv=None) -> int:
         if missing:
             ap.error(f"--query_ids lacks {len(missing)} queries of the qrels split, e.g. {missing[0]!r}")
         q_emb = q_all[[where[qid] for qid in queries]]
-        d_emb = load_npy(args.document_embeddings, len(documents), "document", mmap=args.coarse == "binary" or args.storage == "int8")
+        d_emb = load_npy(args.document_embeddings, len(documents), "document", mmap=host_documents(args))
     else:
         q_emb, d_emb = _embeddings(args, list(queries.values()), documents)
     pairs, rows, excl, below = margin_pairs(qrels, qid2index, docid2index, q_emb, d_emb, args.margin)

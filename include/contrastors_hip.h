@@ -529,6 +529,20 @@ long cx_search_int8_ws_bytes(int M, long N, int k, int nsplit);
 int cx_search_int8_topk(const int8_t* Q, const int8_t* D, const float* q_scale, const float* d_scale, int M, long N, int d,
                         long ldq, long ldd, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
                         int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream);
+/* The int8 scan of an IVF index (faiss IndexIVFScalarQuantizer, QT_8bit with one range per row).  Additive: cx_abi_version
+ * stays 10.  cx_search_int8_topk's operands, score definition, alignment rules and refusals (d % 64 == 0 in [64, 1024], k <= 1024,
+ * byte leading dimensions % 16, 16-B aligned pointers, non-null scales) with cx_search_window_topk's window: row m admits
+ * document n only if min_id[m] < n < end_id[m] (min_id clamped to [-1, N], end_id to [0, N]; NULL = -1 / N everywhere; a row
+ * with end_id <= min_id + 1 has an empty window and is all padding).  A query tile walks the corpus tiles [t0, t1) of its rows'
+ * non-empty windows in one workgroup, as there.  Order (s descending, id ascending), (-inf, -1) padding, ids reported as
+ * positions, M == 0 and N == 0: as cx_search_window_topk.  ws: 16-B aligned, cx_search_int8_window_ws_bytes(M, k)
+ * (== cx_search_window_ws_bytes(M, k)) bytes, need not be initialised.  No value of the window arrays, exclusions or scales
+ * causes an access outside the operands; results under non-finite scales are unspecified. */
+long cx_search_int8_window_ws_bytes(int M, int k);
+int cx_search_int8_window_topk(const int8_t* Q, const int8_t* D, const float* q_scale, const float* d_scale, int M, long N,
+                               int d, long ldq, long ldd, int k, const int64_t* min_id, const int64_t* end_id,
+                               const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
+                               float* out_scores, int64_t* out_ids, void* stream);
 /* backward of  coef * sum_i loss_rows[i]:  Gm[i][j] = coef*scale*(softmax_ij - [j==label_i]) is written to
  * Gmat:(N,G) and GmatT:(G,N) fp32 scratch; dQ:(N,dim) = Gm D, dD:(G,dim) = Gm^T Q (overwritten);
  * dscale_accum (may be NULL): += coef * sum_ij (softmax_ij - y_ij) * (Q D^T)_ij   (d loss / d scale).
