@@ -208,6 +208,11 @@ _SIGS = {
     "cx_search_int8_topk": (i32, [vp, vp, vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "cx_search_int8_window_ws_bytes": (i64, [i32, i32]),
     "cx_search_int8_window_topk": (i32, [vp, vp, vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "cx_pq_half_norm": (i32, [vp, i32, i32, vp, vp]),
+    "cx_pq_assign": (i32, [vp, i64, i32, i64, vp, vp, i32, vp, i64, vp]),
+    "cx_pq_update": (i32, [vp, i64, i32, i64, vp, i64, i32, vp, vp, vp, vp]),
+    "cx_search_pq_ws_bytes": (i64, [i32, i64, i32, i32]),
+    "cx_search_pq_topk": (i32, [vp, vp, vp, i32, i64, i32, i32, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "cx_embed_ln_fwd_typed": (i32, [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp]),
     "cx_embed_ln_bwd_typed": (i32, [vp] * 7 + [i32] + [vp] * 10 + [i64, i32, i32, i32, i32, vp]),
     "cx_embed_ln_bwd_sorted_typed": (i32, [vp] * 7 + [i32] + [vp] * 10 + [i64, i32, i32, i32, i32, i32, vp, vp, vp, vp]),

@@ -27,6 +27,9 @@
 // its own operand staging, K loop (v_mfma_i32_16x16x64_i8) and scaling epilogue; Cand, SearchLds, insert_row<WIN>,
 // merge_lists_kernel<SplitLists> and auto_splits are shared as they are.  cx_search_int8_window_topk is that kernel with
 // WIN = true, the way cx_search_window_topk is search_tiles_kernel<true>: the scan of an IVF index over int8 codes.
+//
+// cx_search_pq_topk is stage 1 over product-quantiser codes (search_pq_tiles_kernel, below the int8 kernel): the bf16 kernel
+// with the document panel gathered from a codebook by the tile's code bytes; everything else is shared as it is.
 #include <type_traits>
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
@@ -215,9 +218,19 @@ CX_DEVICE void init_rows(const SearchParams& p, SearchLdsT<WIN>& L, int m0, int 
     }
 }
 
-template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
-    extern __shared__ __attribute__((aligned(16))) char dsm[];
-    SearchLdsT<WIN>& L = *reinterpret_cast<SearchLdsT<WIN>*>(dsm);
+// What fills the staging registers of the bf16 tile walk below.  RowStage: both panels from bf16 rows (stage).
+struct RowStage {
+    CX_DEVICE void begin_tile(const SearchParams&, int, int) const {}
+    CX_DEVICE void operator()(const SearchParams& p, int m0, int n0, int k0, int tid, uint4 (&sq)[4], uint4 (&sd)[4]) const {
+        stage(p, m0, n0, k0, tid, sq, sd);
+    }
+};
+
+// The walk of one (query tile, split) workgroup over its corpus tiles: the body of search_tiles_kernel<WIN> and of
+// search_pq_tiles_kernel, which differ in the stager only -- the K loop's MFMA order, the epilogue and the insert path are one
+// piece of code, so a score has the same bits whichever way its document panel was filled.
+template <bool WIN, class Params, class Lds, class Stager>
+CX_DEVICE void search_tiles_walk(const Params& p, Lds& L, const Stager& stager) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
     const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
@@ -229,20 +242,21 @@ template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kerne
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * TN;
+        stager.begin_tile(p, n0, tid);
         f32x4_t acc[4][4];   // [query block qb][document block db]
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         uint4 sq[4], sd[4];
-        stage(p, m0, n0, 0, tid, sq, sd);
+        stager(p, m0, n0, 0, tid, sq, sd);
         commit(L.ops, L.ops + PANEL, tid, sq, sd);
         __syncthreads();
         for (int kc = 0; kc < nk; ++kc) {
             const char* qb_ = L.ops + (kc & 1) * 2 * PANEL;
             const char* db_ = qb_ + PANEL;
             // the last chunk is staged twice (unconditional, so the staging registers never leave the register file)
-            stage(p, m0, n0, min(kc + 1, nk - 1) * BK, tid, sq, sd);
+            stager(p, m0, n0, min(kc + 1, nk - 1) * BK, tid, sq, sd);
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 bf16x8_t fq[4], fd[4];
@@ -310,6 +324,11 @@ template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kerne
         __syncthreads();
     }
     if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
+}
+
+template <bool WIN> __global__ __launch_bounds__(256, 1) void search_tiles_kernel(SearchParams p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    search_tiles_walk<WIN>(p, *reinterpret_cast<SearchLdsT<WIN>*>(dsm), RowStage{});
 }
 
 // ---- int8 scalar-quantised rows (cx_search_int8_topk) -----------------------------------------------------------------
@@ -444,6 +463,70 @@ template <bool WIN> __global__ __launch_bounds__(256, 1) void search_int8_tiles_
         __syncthreads();
     }
     if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
+}
+
+// ---- product-quantised rows (cx_search_pq_topk) -----------------------------------------------------------------------
+// Stage 1 over PQ codes (pq.hip): document n is the concatenation of codebook[s][code[n][s]], s < m = d / dsub, bf16 centroids
+// of width dsub in {8, 16, 32, 64}.  search_tiles_kernel<false> with another way of filling the document panel: a 16-byte
+// piece of the panel is 8 consecutive K elements, i.e. one aligned 16-byte slice of ONE centroid, so the panel is gathered from
+// the codebook (256 * d * 2 bytes, resident in L2) instead of read from rows; the corpus itself is read as m bytes per row, once
+// per tile, into LDS.  The query half of the staging, commit / poff, the K loop's MFMA order, the epilogue, insert_row<false>
+// and the split merge are the bf16 kernel's, so a score has the bits cx_search_topk gives the decoded row.
+struct PqParams : SearchParams {     // (D / ldd of the base stay unused)
+    const uint8_t* codes;  // (N, m), byte leading dimension ldc >= m, any alignment
+    const bf16_t* cb;      // (m, 256, dsub) bf16, 16-B aligned
+    long ldc;
+    int m, lsub;           // dsub = 1 << lsub
+    int flat;              // ldc == m and codes 16-B aligned: a tile's codes are one aligned run of bytes
+};
+
+struct PqSearchLds : SearchLds {
+    alignas(16) uint8_t code[TN * 128];   // [row of the tile][m]: the codes of the current corpus tile (m <= 128)
+};
+
+// The tile's codes; row r >= N - n0 holds the codes of row N - 1 (read but never admitted, as the clamped rows of stage).
+CX_DEVICE void load_codes(const PqParams& p, uint8_t* code, int n0, int tid) {
+    const int rows = min(TN, p.N - n0);
+    const int vec = p.flat ? (rows * p.m) & ~15 : 0;   // bytes copied 16 at a time: inside [n0 * m, N * m)
+    const uint8_t* src = p.codes + (int64_t)n0 * p.ldc;
+    for (int b = tid * 16; b < vec; b += 256 * 16) *reinterpret_cast<uint4*>(code + b) = *reinterpret_cast<const uint4*>(src + b);
+    for (int b = vec + tid; b < TN * p.m; b += 256) {
+        const int r = b / p.m, s = b - r * p.m;
+        code[b] = p.codes[(int64_t)min(n0 + r, p.N - 1) * p.ldc + s];
+    }
+}
+
+// stage with the document half gathered: piece (r, c) of chunk k0 is 8 elements from (k0 + 8c) % dsub on of centroid
+// code[r][(k0 + 8c) / dsub] of sub-quantiser (k0 + 8c) / dsub.  A code is a byte: the gather stays inside the codebook.
+CX_DEVICE void stage_pq(const PqParams& p, const uint8_t* code, int m0, int k0, int tid, uint4 (&sq)[4], uint4 (&sd)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int item = tid + 256 * i, r = item >> 3, c = item & 7;
+        const int gm = min(m0 + r, p.M - 1);
+        const int kk = k0 + c * 8, s = kk >> p.lsub;
+        const int cell = s * 256 + code[r * p.m + s];
+        sq[i] = *reinterpret_cast<const uint4*>(p.Q + (int64_t)gm * p.ldq + kk);
+        sd[i] = *reinterpret_cast<const uint4*>(p.cb + ((cell << p.lsub) + (kk & ((1 << p.lsub) - 1))));
+    }
+}
+
+// The stager of the PQ walk: the tile's codes go to LDS before the tile's first chunk (they were last read in the previous
+// tile's K loop, behind that tile's barriers), and every chunk's document half is gathered through them.
+struct PqStage {
+    uint8_t* code;
+    CX_DEVICE void begin_tile(const PqParams& p, int n0, int tid) const {
+        load_codes(p, code, n0, tid);
+        __syncthreads();
+    }
+    CX_DEVICE void operator()(const PqParams& p, int m0, int, int k0, int tid, uint4 (&sq)[4], uint4 (&sd)[4]) const {
+        stage_pq(p, code, m0, k0, tid, sq, sd);
+    }
+};
+
+__global__ __launch_bounds__(256, 1) void search_pq_tiles_kernel(PqParams p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    PqSearchLds& L = *reinterpret_cast<PqSearchLds*>(dsm);
+    search_tiles_walk<false>(p, L, PqStage{L.code});
 }
 
 constexpr int MAXLISTS = 256;       // lists merged into one output row (>= MAXSPLIT)
@@ -625,6 +708,46 @@ int cx_search_int8_topk(const int8_t* Q, const int8_t* D, const float* q_scale, 
         if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel<false>), (int)sizeof(Int8SearchLds<false>)))
             return CX_ERR_LAUNCH;
         hipLaunchKernelGGL(search_int8_tiles_kernel<false>, dim3(tiles_m * ns), dim3(256), sizeof(Int8SearchLds<false>), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    const SplitLists S = {lists, counts, ns, k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_search_pq_ws_bytes(int M, long N, int k, int nsplit) { return cx_search_ws_bytes(M, N, k, nsplit); }
+
+int cx_search_pq_topk(const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int M, long N, int d, int dsub,
+                      long ldq, long ldc, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
+                      int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (dsub != 8 && dsub != 16 && dsub != 32 && dsub != 64) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Q || !out_scores || !out_ids || (N > 0 && (!codes || !codebook || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
+    const int m = d / dsub;
+    if (ldq < d || (ldq % 8) != 0 || (N > 0 && ldc < m)) return CX_ERR_ALIGN;
+    if (((uintptr_t)Q & 15) || ((uintptr_t)codebook & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
+    Cand* lists = reinterpret_cast<Cand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
+    if (N > 0) {
+        PqParams p = {};
+        p.Q = Q; p.ldq = ldq;
+        p.codes = codes; p.cb = codebook; p.ldc = ldc; p.m = m;
+        p.lsub = dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6;
+        p.flat = (ldc == m && ((uintptr_t)codes & 15) == 0) ? 1 : 0;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = ns;
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
+        p.lists = lists; p.counts = counts;
+        const int tiles_m = (M + TM - 1) / TM;
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(&search_pq_tiles_kernel), (int)sizeof(PqSearchLds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(search_pq_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(PqSearchLds), s, p);
         if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
     }
     const SplitLists S = {lists, counts, ns, k};

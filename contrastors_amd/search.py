@@ -24,6 +24,11 @@ which may stay on the host or in a memory-mapped file (csrc/search_binary.hip).
 `IVFInt8Index` is both at once (faiss `IndexIVFScalarQuantizer`, QT_8bit): IVFFlatIndex's lists over Int8FlatIndex's codes,
 scanned by the windowed int8 kernel (cx_search_int8_window_topk); `search_ivf_int8_rescored` is its two-stage form.
 
+`PQFlatIndex` is the format at the small end (faiss `IndexPQ`, 8 bits per sub-quantiser): d / dsub bytes per row, each the
+index of the nearest of 256 trained centroids of a dsub-wide sub-vector (`pq_encode`, csrc/pq.hip), searched with bf16 queries
+by the bf16 tile kernel with its document panel gathered from the codebook (cx_search_pq_topk, csrc/search.hip): bit for bit
+`FlatIPIndex.search` over the decoded rows; `search_pq_rescored` re-scores its candidates exactly.
+
 `encode` is the embedding side: this project's BiEncoder under no_grad, length-sorted batches, results in input order.
 """
 from __future__ import annotations
@@ -1375,6 +1380,378 @@ def search_ivf_int8_rescored(index: IVFInt8Index, vectors, queries, k: int, npro
     qf = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.array(queries, dtype=np.float32))
     qf = _quantizable(qf.to(index.device))   # (once: a page of candidates quantises it again, to the same codes)
     cand = _paged_candidates(lambda kp, ex: index.search(qf, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+
+
+PQ_KSUB = 256                    # centroids per sub-quantiser: a code is one byte
+PQ_DSUBS = (8, 16, 32, 64)       # sub-vector widths: a 16-byte piece of a bf16 row lies inside one centroid
+PQ_DEFAULT_SAMPLE = 1 << 16      # PQFlatIndex.train: rows sampled by default, at most
+PQ_MAX_SAMPLE = 1 << 18          # ... and the largest explicit sample (the update adds in row order, one thread per cell)
+
+
+def _check_pq_dims(d: int, dsub: int) -> int:
+    """-> m = d / dsub (refusals first)."""
+    _check_code_dim(d)
+    if dsub not in PQ_DSUBS:
+        raise ValueError(f"dsub must be one of {PQ_DSUBS}, got {dsub}")
+    return d // dsub
+
+
+def _np_bf16(a: np.ndarray) -> np.ndarray:
+    """fp32 array -> the nearest bf16 values (ties to even) as fp32: the rounding of torch's .to(bfloat16), finite input."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    u = a.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    return r.astype(np.uint32).view(np.float32).reshape(a.shape)
+
+
+def _np_fmaf(a, b, c):
+    """fp32 fmaf of bf16-valued a, b and fp32 c: the float64 sum is exact for such operands (tests/pq_ref.py), so rounding it
+    to fp32 is the one rounding of the fused operation."""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def _pq_half_norm_numpy(shadow: np.ndarray) -> np.ndarray:
+    h = np.zeros(shadow.shape[:-1], np.float32)
+    for j in range(shadow.shape[-1]):
+        h = _np_fmaf(shadow[..., j], shadow[..., j], h)
+    return (np.float32(0.5) * h).astype(np.float32)
+
+
+def _pq_encode_numpy(x: np.ndarray, shadow: np.ndarray) -> np.ndarray:
+    """cx_pq_assign's contract in numpy: every step one IEEE fp32 operation, ties to the lower code."""
+    xb = _np_bf16(x)
+    m, _, dsub = shadow.shape
+    hn = _pq_half_norm_numpy(shadow)
+    codes = np.zeros((xb.shape[0], m), np.uint8)
+    for s in range(m):
+        acc = np.zeros((xb.shape[0], PQ_KSUB), np.float32)
+        for j in range(dsub):
+            acc = _np_fmaf(xb[:, s * dsub + j, None], shadow[s, None, :, j], acc)
+        codes[:, s] = np.argmax((acc - hn[s][None, :]).astype(np.float32), axis=1)
+    return codes
+
+
+def _pq_half_norm_device(shadow: torch.Tensor) -> torch.Tensor:
+    m, _, dsub = shadow.shape
+    hn = torch.empty(m, PQ_KSUB, dtype=torch.float32, device=shadow.device)
+    with torch.cuda.device(shadow.device):
+        _C.check(_C.lib().cx_pq_half_norm(shadow.data_ptr(), m * dsub, dsub, hn.data_ptr(), _C.cur_stream()), "cx_pq_half_norm")
+    return hn
+
+
+def _pq_assign_device(xb: torch.Tensor, shadow: torch.Tensor, hn: torch.Tensor, codes: torch.Tensor) -> None:
+    """xb (n, d) bf16 on the GPU (unit column stride) -> codes (n, m) uint8 view (unit column stride), in place."""
+    n, d = xb.shape
+    m, _, dsub = shadow.shape
+    if n:
+        with torch.cuda.device(xb.device):
+            _C.check(_C.lib().cx_pq_assign(xb.data_ptr(), n, d, xb.stride(0) if n > 1 else d, shadow.data_ptr(), hn.data_ptr(),
+                                           dsub, codes.data_ptr(), codes.stride(0) if n > 1 else m, _C.cur_stream()),
+                     "cx_pq_assign")
+
+
+def _pq_rows(x: torch.Tensor) -> torch.Tensor:
+    """A GPU tensor as cx_pq_assign takes it: bf16 (other dtypes rounded as FlatIPIndex.add rounds), unit column stride, rows
+    not overlapping."""
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x
+
+
+def _check_codebooks(codebooks, d: Optional[int] = None, dsub: Optional[int] = None):
+    shape = tuple(np.shape(codebooks))
+    if len(shape) != 3 or shape[1] != PQ_KSUB or shape[2] not in PQ_DSUBS:
+        raise ValueError(f"expected (m, {PQ_KSUB}, dsub) codebooks with dsub in {PQ_DSUBS}, got shape {shape}")
+    if d is not None and (shape[2] != dsub or shape[0] * shape[2] != d):
+        raise ValueError(f"expected ({d // dsub}, {PQ_KSUB}, {dsub}) codebooks, got shape {shape}")
+    _check_code_dim(shape[0] * shape[2])
+    return shape
+
+
+def pq_encode(x, codebooks):
+    """Product-quantiser codes of the rows of x (n, d) against codebooks (m, 256, dsub), m * dsub = d -> uint8 (n, m): faiss
+    IndexPQ's encoding with 8 bits per sub-quantiser under inner-product-free nearest-centroid assignment.  x is rounded to bf16
+    (as FlatIPIndex.add rounds) and so are the codebooks (PQFlatIndex.codebooks already is the bf16 shadow); per sub-vector
+    the code is the arg-max of fmaf-chain(x . c) - 0.5f * fmaf-chain(c . c), ties to the lower code (tests/pq_ref.py is the
+    contract).  A tensor on the GPU goes through cx_pq_assign (a row stride is honoured); a CPU tensor or a numpy array through
+    numpy.  Same bytes either way for finite input; torch in -> torch out."""
+    is_torch = isinstance(x, torch.Tensor)
+    if not is_torch:
+        x = np.asarray(x)
+    if x.ndim != 2:
+        raise ValueError(f"expected a (n, d) array, got shape {tuple(x.shape)}")
+    m, _, dsub = _check_codebooks(codebooks)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    if d != m * dsub:
+        raise ValueError(f"expected a (n, {m * dsub}) array for ({m}, {PQ_KSUB}, {dsub}) codebooks, got shape {tuple(x.shape)}")
+    if not is_torch or x.device.type != "cuda":
+        cb = codebooks.detach().cpu().float().numpy() if isinstance(codebooks, torch.Tensor) else np.asarray(codebooks, np.float32)
+        codes = _pq_encode_numpy(x.float().numpy() if is_torch else x, _np_bf16(cb))
+        return torch.from_numpy(codes) if is_torch else codes
+    shadow = torch.as_tensor(codebooks).to(device=x.device, dtype=torch.bfloat16).contiguous()
+    codes = torch.empty(n, m, dtype=torch.uint8, device=x.device)
+    _pq_assign_device(_pq_rows(x), shadow, _pq_half_norm_device(shadow), codes)
+    return codes
+
+
+def pq_train_rows(n: int, sample: Optional[int], seed: int):
+    """The rows PQFlatIndex.train fits on and starts from -> (sample rows (ns,) int64 ascending, or None = all n rows;
+    initial rows (256,) int64, positions INSIDE the sample).  The sample is KMeans.fit(sample=)'s seeded choice; the initial
+    centroids of every sub-quantiser are the sub-vectors of the first 256 rows of a permutation seeded the same way."""
+    rows = None
+    ns = n
+    if sample is not None and int(sample) < n:
+        g = torch.Generator().manual_seed(seed)
+        rows = torch.randperm(n, generator=g)[: int(sample)].sort().values
+        ns = int(sample)
+    g = torch.Generator().manual_seed(seed)
+    return rows, torch.randperm(ns, generator=g)[:PQ_KSUB]
+
+
+class PQFlatIndex:
+    """Maximum-inner-product index over product-quantised rows on one GPU (faiss IndexPQ, 8 bits per sub-quantiser, asymmetric
+    scoring): d / dsub bytes per vector -- with dsub = 8 what BinaryFlatIndex keeps -- where FlatIPIndex keeps 2 d.  A row is
+    cut into m = d / dsub sub-vectors, each stored as the index of the nearest of 256 trained centroids; queries stay bf16.
+    The search kernel (cx_search_pq_topk, csrc/search.hip) is the bf16 tile kernel with the document panel gathered from the
+    codebook in LDS-staging order, so `search` equals `FlatIPIndex.search` over `decode()` bit for bit.  Same surface as
+    FlatIPIndex / Int8FlatIndex; search_pq_rescored re-scores its candidates exactly against the float rows.
+
+    Not here: IVF lists and residual encoding, OPQ rotations, other code widths, a look-up-table scan, save / load (codebooks go
+    in and out as arrays), more than one GPU."""
+
+    def __init__(self, d: int, dsub: int = 8, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
+        self.m = _check_pq_dims(int(d), int(dsub))
+        self.d, self.dsub = int(d), int(dsub)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("PQFlatIndex runs on the GPU (cx_search_pq_topk); there is no CPU path")
+        self.workspace_bytes = int(workspace_bytes)
+        self.seed = int(seed)
+        self._masters: Optional[torch.Tensor] = None   # (m, 256, dsub) fp32
+        self._shadow: Optional[torch.Tensor] = None    # ... rounded to bf16: what encodes, decodes and scores
+        self._hn: Optional[torch.Tensor] = None        # (m, 256) fp32 half norms of the shadow
+        self._store: Optional[torch.Tensor] = None     # (capacity, m) uint8; rows [0, ntotal) are the corpus
+        self.ntotal = 0
+
+    def reset(self) -> None:
+        """Drop the stored rows; the codebooks stay."""
+        self._store = None
+        self.ntotal = 0
+
+    @property
+    def is_trained(self) -> bool:
+        return self._shadow is not None
+
+    def _require_trained(self) -> None:
+        if self._shadow is None:
+            raise RuntimeError("PQFlatIndex has no codebooks yet: call train() first")
+
+    @property
+    def codebooks(self) -> torch.Tensor:
+        """(m, 256, dsub) bf16: the shadow of the trained masters, the only table used to encode, decode and score."""
+        self._require_trained()
+        return self._shadow
+
+    @property
+    def masters(self) -> torch.Tensor:
+        """(m, 256, dsub) fp32: what the Lloyd updates wrote."""
+        self._require_trained()
+        return self._masters
+
+    @property
+    def half_norms(self) -> torch.Tensor:
+        """(m, 256) fp32: half the squared norm of every shadow centroid, the bias of the assignment."""
+        self._require_trained()
+        return self._hn
+
+    def train(self, x=None, max_iter: int = 25, sample: Optional[int] = None, codebooks=None) -> None:
+        """Fit the m x 256 centroids to x (a tensor anywhere, an array or a memmap; host sources are sampled on the host) with
+        max_iter Lloyd steps (cx_pq_assign, cx_pq_update) from seeded initial rows -- the same x and seed give the same bits;
+        no convergence test, no restarts -- or take a given (m, 256, dsub) table as the masters.  sample: fit on that many rows,
+        a seeded subsample (default min(n, 65 536); explicit values from 256 to 262 144)."""
+        if (x is None) == (codebooks is None):
+            raise ValueError("train: give either the training rows or codebooks=")
+        if self.ntotal:
+            raise RuntimeError("train: the index holds rows encoded with the current codebooks; reset() first")
+        if codebooks is not None:
+            _check_codebooks(codebooks, self.d, self.dsub)
+            self._masters = torch.as_tensor(codebooks).to(device=self.device, dtype=torch.float32).clone().contiguous()
+            self._shadow = self._masters.to(torch.bfloat16)
+            self._hn = _pq_half_norm_device(self._shadow)
+            return
+        if len(np.shape(x)) != 2 or np.shape(x)[1] != self.d:
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(x))}")
+        n = int(np.shape(x)[0])
+        max_iter = int(max_iter)
+        if max_iter < 0:
+            raise ValueError(f"max_iter must not be negative, got {max_iter}")
+        if sample is not None and not PQ_KSUB <= int(sample) <= PQ_MAX_SAMPLE:
+            raise ValueError(f"sample must be in [{PQ_KSUB}, {PQ_MAX_SAMPLE}], got {sample}")
+        ns = min(n, PQ_DEFAULT_SAMPLE if sample is None else int(sample))
+        if ns < PQ_KSUB:
+            raise ValueError(f"train: {PQ_KSUB} centroids need at least {PQ_KSUB} rows, got {ns}")
+        rows, first = pq_train_rows(n, ns, self.seed)
+        if rows is None:
+            xs = x
+        elif isinstance(x, torch.Tensor):
+            xs = x[rows.to(x.device)]
+        else:
+            xs = np.asarray(x[rows.numpy()], dtype=np.float32)
+        xs = xs if isinstance(xs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(xs, dtype=np.float32)))
+        xb = _pq_rows(xs.to(self.device))
+        if xb.data_ptr() % 16 or xb.stride(0) % 8:
+            xb = xb.clone(memory_format=torch.contiguous_format)
+        masters = xb[first.to(self.device)].float().view(PQ_KSUB, self.m, self.dsub).transpose(0, 1).contiguous()
+        shadow = masters.to(torch.bfloat16)
+        hn = _pq_half_norm_device(shadow)
+        codes = torch.empty(ns, self.m, dtype=torch.uint8, device=self.device)
+        h = _C.lib()
+        with torch.cuda.device(self.device):
+            stream = _C.cur_stream()
+            for _ in range(max_iter):
+                _pq_assign_device(xb, shadow, hn, codes)
+                _C.check(h.cx_pq_update(xb.data_ptr(), ns, self.d, xb.stride(0), codes.data_ptr(), self.m, self.dsub,
+                                        masters.data_ptr(), shadow.data_ptr(), hn.data_ptr(), stream), "cx_pq_update")
+        self._masters, self._shadow, self._hn = masters, shadow, hn
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """The stored codes, (ntotal, m) uint8 (a view)."""
+        if self._store is None:
+            return torch.empty(0, self.m, dtype=torch.uint8, device=self.device)
+        return self._store[: self.ntotal]
+
+    def reserve(self, n: int) -> None:
+        """Allocate room for n codes in total, so that adding a corpus in chunks never copies it."""
+        if n > MAX_NTOTAL:
+            raise ValueError(f"PQFlatIndex holds at most {MAX_NTOTAL} vectors")
+        cap = 0 if self._store is None else self._store.shape[0]
+        if n > cap:
+            grown = torch.empty(n, self.m, dtype=torch.uint8, device=self.device)
+            if self.ntotal:
+                grown[: self.ntotal].copy_(self._store[: self.ntotal])
+            self._store = grown
+
+    def _is_codes(self, x) -> bool:
+        return (x.dtype == torch.uint8) if isinstance(x, torch.Tensor) else (np.asarray(x).dtype == np.uint8)
+
+    def add(self, x) -> None:
+        """Append rows: float vectors (a tensor anywhere, an array or a memmap) are encoded on the device 65 536 rows at a time
+        (pq_encode's contract), a uint8 (n, m) array is taken as codes."""
+        if len(np.shape(x)) != 2:
+            raise ValueError(f"expected a 2-d array, got shape {tuple(np.shape(x))}")
+        n = int(np.shape(x)[0])
+        is_codes = self._is_codes(x)
+        if np.shape(x)[1] != (self.m if is_codes else self.d):
+            raise ValueError(f"expected a (n, {self.d}) array or (n, {self.m}) uint8 codes, got shape {tuple(np.shape(x))}")
+        if self.ntotal + n > MAX_NTOTAL:
+            raise ValueError(f"PQFlatIndex holds at most {MAX_NTOTAL} vectors")
+        self._require_trained()
+        if is_codes:
+            self.reserve(self.ntotal + n)
+            self._store[self.ntotal: self.ntotal + n].copy_(torch.as_tensor(x if isinstance(x, torch.Tensor) else np.asarray(x)))
+        else:
+            self.reserve(self.ntotal + n)
+            out = self._store[self.ntotal: self.ntotal + n]
+            for r0, r1, part in _float_chunks(x, n, self.device):
+                _pq_assign_device(_pq_rows(part), self._shadow, self._hn, out[r0:r1])
+        self.ntotal += n
+
+    def decode(self, ids=None) -> torch.Tensor:
+        """-> (n, d) bf16: the rows the codes stand for (all of them, or those of the given ids), the concatenation of
+        codebooks[s][codes[n][s]]."""
+        self._require_trained()
+        codes = self.codes
+        if ids is not None:
+            ids = torch.as_tensor(ids if isinstance(ids, torch.Tensor) else np.asarray(ids)).to(device=self.device, dtype=torch.int64)
+            if ids.dim() != 1 or (ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal)):
+                raise ValueError(f"decode: expected a 1-d list of ids in [0, {self.ntotal})")
+            codes = codes[ids]
+        s = torch.arange(self.m, device=self.device)[None, :]
+        return self._shadow[s, codes.to(torch.int64)].reshape(codes.shape[0], self.d)
+
+    def batch_rows(self, M: int, k: int) -> int:
+        """The largest query batch (all of M, else halved down to a multiple of 128) whose workspace fits the bound."""
+        h = _C.lib()
+        m = M
+        while m > 128 and h.cx_search_pq_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
+            m = max(128, (m // 2) // 128 * 128)
+        return m
+
+    def search(self, queries, k: int, exclude=None, below=None, nsplit: int = 0):
+        """-> (scores (M, k) float32, ids (M, k) int64): FlatIPIndex.search over the decoded rows, bit for bit -- per query the k
+        largest inner products of the bf16 query with the decoded vectors, descending, ties to the lower id; missing entries are
+        (-inf, -1).  exclude, below, nsplit, numpy in -> numpy out: as FlatIPIndex.search."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        if len(np.shape(queries)) != 2 or np.shape(queries)[1] != self.d:
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(queries))}")
+        M = int(np.shape(queries)[0])
+        xptr, xids = _exclusion_csr_host(exclude, M)
+        if below is not None:
+            n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
+            if n_below != M:
+                raise ValueError(f"below has {n_below} entries for {M} queries")
+        self._require_trained()
+        bel = None
+        if below is not None:
+            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
+            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        q = _to_device_2d(queries, self.d, self.device)
+        if xptr is not None:
+            xptr = xptr.to(self.device)
+            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
+        scores = torch.empty(M, k, dtype=torch.float32, device=self.device)
+        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
+        if M:
+            h = _C.lib()
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                mb = self.batch_rows(M, k)
+                ws = None
+                if self.ntotal:
+                    last = M - (M - 1) // mb * mb
+                    nbytes = max(h.cx_search_pq_ws_bytes(mb, self.ntotal, k, nsplit),
+                                 h.cx_search_pq_ws_bytes(last, self.ntotal, k, nsplit))
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                D = self.codes
+                for b0 in range(0, M, mb):
+                    m = min(mb, M - b0)
+                    _C.check(h.cx_search_pq_topk(q[b0].data_ptr(), D.data_ptr() if self.ntotal else None,
+                                                 self._shadow.data_ptr(), m, self.ntotal, self.d, self.dsub, self.d, self.m, k,
+                                                 None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
+                                                 None if bel is None else bel[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
+                                                 scores[b0].data_ptr(), ids[b0].data_ptr(), stream), "cx_search_pq_topk")
+        if as_numpy:
+            return scores.cpu().numpy(), ids.cpu().numpy()
+        return scores, ids
+
+
+def search_pq_rescored(index: PQFlatIndex, vectors, queries, k: int, rescore_factor: int = 4, exclude=None, below=None):
+    """Coarse PQ search + exact re-scoring: the min(k * rescore_factor, 4096) best PQ scores of `index` per query, then the k
+    best of those by exact inner product with `vectors` (the corpus the codes were made from: device bf16 rows, a host array or
+    a memmap; see rescore).  queries: float rows.  exclude applies to the coarse stage, below to the exact score.
+    -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit when the candidate lists cover the corpus.  Lists longer
+    than the kernel's k bound (1024) are fetched in pages (_paged_candidates)."""
+    k = int(k)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    as_numpy = not isinstance(queries, torch.Tensor)
+    if len(np.shape(queries)) != 2 or np.shape(queries)[1] != index.d:
+        raise ValueError(f"expected a (n, {index.d}) array, got shape {tuple(np.shape(queries))}")
+    M = int(np.shape(queries)[0])
+    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
+    if below is not None:
+        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
+        if n_below != M:
+            raise ValueError(f"below has {n_below} entries for {M} queries")
+    index._require_trained()
+    qd = _to_device_2d(queries, index.d, index.device)
+    cand = _paged_candidates(lambda kp, ex: index.search(qd, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
     return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
 
 

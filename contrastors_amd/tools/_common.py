@@ -84,12 +84,14 @@ def load_tower(checkpoint, device: str):
 COARSE = ("exact", "binary")
 STORAGE = ("bf16", "int8")
 IVF_STORAGE = ("bf16", "int8")
-ADD_ROWS = 1 << 18   # binary / int8: document rows encoded per upload
+PQ_DSUB = (0, 8, 16, 32, 64)   # --pq_dsub: 0 = off
+ADD_ROWS = 1 << 18   # binary / int8 / pq: document rows encoded per upload
 
 
 def host_documents(args) -> bool:
     """The searches that keep the document rows on the host: the .npy is memory-mapped, not read."""
-    return args.coarse == "binary" or args.storage == "int8" or getattr(args, "ivf_storage", "bf16") == "int8"
+    return (args.coarse == "binary" or args.storage == "int8" or getattr(args, "ivf_storage", "bf16") == "int8"
+            or bool(getattr(args, "pq_dsub", 0)))
 
 
 def add_search_arguments(ap) -> None:
@@ -98,7 +100,7 @@ def add_search_arguments(ap) -> None:
                          "sign codes (1/16 of the memory), then exact re-scoring of k * rescore_factor candidates against "
                          "the memory-mapped document .npy")
     ap.add_argument("--rescore_factor", type=int, default=4,
-                    help="binary / int8: candidates re-scored per returned neighbour (k * rescore_factor, at most 4096)")
+                    help="binary / int8 / pq: candidates re-scored per returned neighbour (k * rescore_factor, at most 4096)")
     ap.add_argument("--storage", choices=STORAGE, default="bf16",
                     help="bf16: the corpus on the device as bf16 rows; int8: as int8 codes + one fp32 scale per row (half the "
                          "memory), searched by int8 score, then exact re-scoring of k * rescore_factor candidates against the "
@@ -114,10 +116,39 @@ def add_search_arguments(ap) -> None:
                     help="with --ivf_lists K: bf16: the lists hold bf16 rows (IVFFlatIndex); int8: int8 codes + one fp32 scale "
                          "per row (IVFInt8Index, half the memory), searched by int8 score, then exact re-scoring of "
                          "k * rescore_factor candidates against the memory-mapped document .npy")
+    ap.add_argument("--pq_dsub", type=int, choices=PQ_DSUB, default=0,
+                    help="S > 0: the corpus on the device as product-quantiser codes, one byte per S dimensions "
+                         "(PQFlatIndex; S = 8: 1/16 of the bf16 memory), searched by PQ score, then exact re-scoring of "
+                         "k * rescore_factor candidates against the memory-mapped document .npy (with --coarse exact and "
+                         "--storage bf16, without --ivf_lists); 0 = off")
+    ap.add_argument("--pq_sample", type=int, default=None,
+                    help="fit the PQ codebooks on that many sampled documents (default min(n, 65536); 256 to 262144)")
+    ap.add_argument("--pq_iters", type=int, default=25, help="Lloyd iterations of the PQ codebook fit")
+    ap.add_argument("--pq_codebooks", default=None, help="(d / S, 256, S) .npy codebooks to use instead of fitting them")
+
+
+def check_pq_arguments(ap, args) -> dict:
+    """Refuse --pq_* combinations the search cannot serve (ap.error) -> the pq_* keyword arguments of search() (none when off)."""
+    if not args.pq_dsub:
+        if args.pq_sample is not None or args.pq_codebooks is not None:
+            ap.error("--pq_sample and --pq_codebooks need --pq_dsub S")
+        return {}
+    if args.coarse != "exact":
+        ap.error("--pq_dsub goes with --coarse exact only")
+    if getattr(args, "storage", "bf16") != "bf16":
+        ap.error("--pq_dsub does not go with --storage int8")
+    if args.ivf_lists:
+        ap.error("--pq_dsub does not go with --ivf_lists")
+    if args.pq_iters < 0 or (args.pq_sample is not None and not 256 <= args.pq_sample <= 262144):
+        ap.error("--pq_iters must not be negative and --pq_sample must be in [256, 262144]")
+    return {"pq_dsub": args.pq_dsub, "pq_sample": args.pq_sample, "pq_iters": args.pq_iters,
+            "pq_codebooks": args.pq_codebooks}
 
 
 def check_search_arguments(ap, args) -> dict:
-    """Refuse flag combinations the search cannot serve (ap.error) -> the ivf_* keyword arguments of search()."""
+    """Refuse flag combinations the search cannot serve (ap.error) -> the ivf_* (and, with --pq_dsub, pq_*) keyword arguments
+    of search()."""
+    pq = check_pq_arguments(ap, args) if hasattr(args, "pq_dsub") else {}
     if getattr(args, "storage", "bf16") == "int8":
         if args.coarse != "exact":
             ap.error("--storage int8 goes with --coarse exact only")
@@ -130,7 +161,7 @@ def check_search_arguments(ap, args) -> dict:
             ap.error("--ivf_nprobe, --ivf_centroids and --ivf_sample need --ivf_lists K")
         if getattr(args, "ivf_storage", "bf16") != "bf16":
             ap.error("--ivf_storage needs --ivf_lists K")
-        return {}
+        return pq
     if args.coarse != "exact":
         ap.error("--ivf_lists goes with --coarse exact only")
     nprobe = min(8, args.ivf_lists) if args.ivf_nprobe is None else args.ivf_nprobe
@@ -159,7 +190,8 @@ def _fit_sample(doc_emb, sample: Optional[int], seed: int = 0):
 
 def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, coarse: str = "exact",
            rescore_factor: int = 4, ivf_lists: int = 0, ivf_nprobe: Optional[int] = None, ivf_centroids=None,
-           ivf_sample: Optional[int] = None, ivf_iters: int = 25, storage: str = "bf16", ivf_storage: str = "bf16"):
+           ivf_sample: Optional[int] = None, ivf_iters: int = 25, storage: str = "bf16", ivf_storage: str = "bf16",
+           pq_dsub: int = 0, pq_sample: Optional[int] = None, pq_iters: int = 25, pq_codebooks=None):
     """-> (scores, ids) numpy.  coarse="exact": exact inner-product top-k over the bf16 corpus (FlatIPIndex).
     coarse="binary": Hamming top-(k * rescore_factor) over sign codes (BinaryFlatIndex), re-scored exactly against doc_emb,
     which stays on the host (an array or a memmap); equal to "exact" once the candidates cover the corpus.
@@ -172,11 +204,15 @@ def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, co
     ivf_storage="int8" (with ivf_lists): the lists hold int8 codes (IVFInt8Index): doc_emb stays on the host and is added
     ADD_ROWS rows at a time; the centroids are fitted on the ivf_sample rows gathered on the host (without ivf_sample: on all
     of doc_emb, uploaded as bf16 for the fit); the int8 top-(k * rescore_factor) of the probed lists are re-scored exactly
-    against doc_emb; equal to "exact" when every list is probed and the candidates cover the corpus."""
+    against doc_emb; equal to "exact" when every list is probed and the candidates cover the corpus.
+    pq_dsub = S > 0 (with "exact" and "bf16", without ivf_lists): PQ top-(k * rescore_factor) over one-byte-per-S-dimensions
+    codes (PQFlatIndex; codebooks fitted to doc_emb with pq_iters Lloyd steps on pq_sample rows gathered on the host, or read
+    from the .npy path / array pq_codebooks), re-scored exactly against doc_emb, which stays on the host; equal to "exact" once
+    the candidates cover the corpus."""
     import torch
 
-    from ..search import (BinaryFlatIndex, FlatIPIndex, Int8FlatIndex, IVFFlatIndex, IVFInt8Index, search_binary_rescored,
-                          search_int8_rescored, search_ivf_int8_rescored)
+    from ..search import (BinaryFlatIndex, FlatIPIndex, Int8FlatIndex, IVFFlatIndex, IVFInt8Index, PQFlatIndex,
+                          search_binary_rescored, search_int8_rescored, search_ivf_int8_rescored, search_pq_rescored)
 
     if coarse not in COARSE:
         raise ValueError(f"coarse must be one of {COARSE}, got {coarse!r}")
@@ -190,6 +226,23 @@ def search(doc_emb, query_emb, k: int, device: str, exclude=None, below=None, co
         raise ValueError("ivf_lists goes with coarse='exact' only")
     if storage == "int8" and (coarse != "exact" or ivf_lists):
         raise ValueError("storage='int8' goes with coarse='exact' and without ivf_lists only")
+    if pq_dsub not in PQ_DSUB:
+        raise ValueError(f"pq_dsub must be one of {PQ_DSUB}, got {pq_dsub!r}")
+    if pq_dsub and (coarse != "exact" or storage != "bf16" or ivf_lists):
+        raise ValueError("pq_dsub goes with coarse='exact', storage='bf16' and without ivf_lists only")
+    if pq_dsub:
+        n, d = np.shape(doc_emb)
+        index = PQFlatIndex(d, int(pq_dsub), device=device)
+        if pq_codebooks is not None:
+            table = np.load(pq_codebooks) if isinstance(pq_codebooks, (str, Path)) else pq_codebooks
+            index.train(codebooks=np.asarray(table, dtype=np.float32))
+        else:
+            index.train(doc_emb, max_iter=pq_iters, sample=pq_sample)
+        index.reserve(n)
+        for r0 in range(0, n, ADD_ROWS):
+            index.add(np.asarray(doc_emb[r0: r0 + ADD_ROWS], dtype=np.float32))
+        return search_pq_rescored(index, doc_emb, np.asarray(query_emb, dtype=np.float32), k, rescore_factor,
+                                  exclude=exclude, below=below)
     if storage == "int8":
         n, d = np.shape(doc_emb)
         index = Int8FlatIndex(d, device=device)

@@ -543,6 +543,37 @@ int cx_search_int8_window_topk(const int8_t* Q, const int8_t* D, const float* q_
                                int d, long ldq, long ldd, int k, const int64_t* min_id, const int64_t* end_id,
                                const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
                                float* out_scores, int64_t* out_ids, void* stream);
+/* ---- product-quantised index (faiss IndexPQ, 8 bits per sub-quantiser; csrc/pq.hip, csrc/search.hip).  Additive:
+ *          cx_abi_version stays 10. ---------------------------------------------------------------------------------------
+ * A row of width d (% 64 == 0 in [64, 1024]) is cut into m = d / dsub sub-vectors, dsub in {8, 16, 32, 64} (CX_ERR_SHAPE
+ * otherwise); sub-quantiser s has 256 centroids.  Codebooks: masters:(m,256,dsub) fp32, shadow:(m,256,dsub) bf16 = the
+ * masters rounded to nearest even, 16-B aligned, half_norm:(m,256) fp32.  Only the shadow encodes, decodes and scores.  Every
+ * step below is one correctly rounded fp32 operation in the order given (tests/pq_ref.py is the contract).
+ * cx_pq_half_norm: half_norm[s][c] = 0.5f * h, h = 0, h = fmaf(c_j, c_j, h) for j ascending over the bf16 centroid.
+ * cx_pq_assign: X:(n,d) bf16, leading dimension ldx ELEMENTS >= d.  Per row and s: acc = 0, acc = fmaf(x_j, c_j, acc) for j
+ * ascending over the sub-vector, score = acc - half_norm[s][c]; code = the arg-max over c, ties to the lower c.  codes:(n,m)
+ * uint8, byte leading dimension ldc >= m, any alignment (ldc == m is legal for every m).  A code is in [0, 256) whatever the
+ * input; results under non-finite input are otherwise unspecified.
+ * cx_pq_update (the second half of a Lloyd step, n <= 2^24): per (s, c) the fp32 sum of the sub-vectors of the rows whose code
+ * is c, added element-wise in ASCENDING ROW ORDER; masters[s][c] = sum / count where count > 0, an empty cell keeps its
+ * master; shadow and half_norm of every cell are rewritten.  Deterministic, no atomics.
+ * Both: n == 0 is CX_OK without a launch (cx_pq_update then leaves shadow and half_norm alone). */
+int cx_pq_half_norm(const uint16_t* shadow, int d, int dsub, float* half_norm, void* stream);
+int cx_pq_assign(const uint16_t* X, long n, int d, long ldx, const uint16_t* shadow, const float* half_norm, int dsub,
+                 uint8_t* codes, long ldc, void* stream);
+int cx_pq_update(const uint16_t* X, long n, int d, long ldx, const uint8_t* codes, long ldc, int dsub, float* masters,
+                 uint16_t* shadow, float* half_norm, void* stream);
+/* Top-k over such codes: cx_search_topk argument for argument with (codes, codebook, dsub, ldc) in place of (D, ldd).
+ * Document n is the concatenation of codebook[s][codes[n][s]], s < m; codebook = the bf16 shadow, 16-B aligned
+ * (CX_ERR_ALIGN); codes:(N,m) uint8, byte leading dimension ldc >= m (CX_ERR_ALIGN), any alignment.  The score of (m, n) has
+ * the bits cx_search_topk gives query m and the decoded row n (the same MFMAs in the same K order), so the whole result is
+ * cx_search_topk's over the decoded corpus: k, the exclusion CSR, below, nsplit (no effect on the result), the order, the
+ * (-inf, -1) padding, the error codes, N == 0 and M == 0 as there.  ws: 16-B aligned, cx_search_pq_ws_bytes(M, N, k, nsplit)
+ * (== cx_search_ws_bytes) bytes.  A code is a byte, so no value of codes reads outside the codebook. */
+long cx_search_pq_ws_bytes(int M, long N, int k, int nsplit);
+int cx_search_pq_topk(const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int M, long N, int d, int dsub,
+                      long ldq, long ldc, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
+                      int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream);
 /* backward of  coef * sum_i loss_rows[i]:  Gm[i][j] = coef*scale*(softmax_ij - [j==label_i]) is written to
  * Gmat:(N,G) and GmatT:(G,N) fp32 scratch; dQ:(N,dim) = Gm D, dD:(G,dim) = Gm^T Q (overwritten);
  * dscale_accum (may be NULL): += coef * sum_ij (softmax_ij - y_ij) * (Q D^T)_ij   (d loss / d scale).
