@@ -36,6 +36,19 @@ CX_DEVICE uint32_t pack_bf16x2(float lo, float hi) {
 }
 CX_DEVICE bf16_t f32_to_bf16(float f) { return (bf16_t)(pack_bf16x2(f, 0.f) & 0xffffu); }
 
+// One fp32 addition / subtraction, round to nearest even, spelled as the instruction: a run of independent adds written in C++
+// may be paired into two-wide packed adds by the vectoriser; where a contract says "one fp32 addition" these stay single ones.
+CX_DEVICE float fadd_single(float a, float b) {
+    float r;
+    asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+CX_DEVICE float fsub_single(float a, float b) {
+    float r;
+    asm("v_sub_f32_e32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
 // One lane's 16 B of the HBM-bound kernels: 8 bf16 of a uint4 as 8 floats and back (one rounding per value), and 8
 // consecutive fp32 of a bias / gamma / beta vector as two 16-B loads, not eight scalar ones (bias_gelu_fwd was
 // VMEM-issue-bound on them).

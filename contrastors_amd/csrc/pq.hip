@@ -10,6 +10,10 @@
 // Every step is one correctly rounded fp32 operation, spelled (__builtin_fmaf, __fsub_rn, __fadd_rn, __fdiv_rn, __fmul_rn) so
 // that no contraction choice is left to the compiler.  A code is a loop index in [0, 256): non-finite input cannot index out of
 // range (a NaN score never wins; a row of NaNs gets code 0) and is otherwise unspecified.  No float atomics anywhere.
+//
+// cx_pq_assign_residual (the encoder of IVFPQIndex; tests/ivf_pq_ref.py) is assign over r = x - c_l, l the row's list:
+//   r_j = bf16(f32(x_j) - f32(c_l,j)), one fp32 subtraction and one rounding to nearest even per element, formed in registers
+//   from the row and its centroid's slice; the residuals of the corpus are never written anywhere.
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
 
@@ -36,10 +40,19 @@ __global__ __launch_bounds__(256) void pq_half_norm_kernel(const bf16_t* __restr
 // Workgroup (s, row block): the 256 x DSUB bf16 slice of sub-quantiser s (4 - 32 KiB) and its half-norms sit in LDS; a lane
 // owns one row, keeps its sub-vector in registers and walks the 256 centroids, so that a wave's centroid reads are
 // same-address broadcasts.  Codes leave as single bytes: any byte leading dimension >= m is legal, m = 1 and ldc == m included.
-template <int DSUB, bool VEC>
+// RES: the lane's sub-vector is the residual to the same slice of its list's centroid (ResidualSrc), the label clamped into
+// [0, nlist) for the read.
+struct ResidualSrc {
+    const int* labels;     // (n) list of every row
+    const bf16_t* cen;     // (nlist, d) bf16, leading dimension ldcen elements
+    long ldcen;
+    int nlist;
+};
+
+template <int DSUB, bool VEC, bool RES>
 __global__ __launch_bounds__(256) void pq_assign_kernel(const bf16_t* __restrict__ X, long ldx, long n,
                                                         const bf16_t* __restrict__ shadow, const float* __restrict__ half_norm,
-                                                        uint8_t* __restrict__ codes, long ldc) {
+                                                        uint8_t* __restrict__ codes, long ldc, ResidualSrc res) {
     __shared__ __attribute__((aligned(16))) bf16_t cb[KSUB * DSUB];
     __shared__ float hn[KSUB];
     const int s = blockIdx.x, tid = threadIdx.x;
@@ -63,6 +76,22 @@ __global__ __launch_bounds__(256) void pq_assign_kernel(const bf16_t* __restrict
             } else {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) x[j0 + e] = bf16_to_f32(xp[j0 + e]);
+            }
+        }
+        if constexpr (RES) {
+            const int l = min(max(res.labels[row], 0), res.nlist - 1);
+            const bf16_t* cp = res.cen + l * res.ldcen + s * DSUB;
+#pragma unroll
+            for (int j0 = 0; j0 < DSUB; j0 += 8) {
+                float f[8];
+                if constexpr (VEC) {
+                    unpack8(*reinterpret_cast<const uint4*>(cp + j0), f);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) f[e] = bf16_to_f32(cp[j0 + e]);
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[j0 + e] = bf16_to_f32(f32_to_bf16(fsub_single(x[j0 + e], f[e])));
             }
         }
         float best = -INFINITY;
@@ -154,14 +183,14 @@ bool dsub_ok(int d, int dsub) {
     return d >= 64 && d <= 1024 && (d % 64) == 0 && (dsub == 8 || dsub == 16 || dsub == 32 || dsub == 64);
 }
 
-template <bool VEC>
+template <bool VEC, bool RES>
 void launch_assign(int dsub, dim3 grid, hipStream_t st, const bf16_t* X, long ldx, long n, const bf16_t* shadow,
-                   const float* hn, uint8_t* codes, long ldc) {
+                   const float* hn, uint8_t* codes, long ldc, ResidualSrc res = {}) {
     switch (dsub) {
-        case 8: hipLaunchKernelGGL((pq_assign_kernel<8, VEC>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc); break;
-        case 16: hipLaunchKernelGGL((pq_assign_kernel<16, VEC>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc); break;
-        case 32: hipLaunchKernelGGL((pq_assign_kernel<32, VEC>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc); break;
-        default: hipLaunchKernelGGL((pq_assign_kernel<64, VEC>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc); break;
+        case 8: hipLaunchKernelGGL((pq_assign_kernel<8, VEC, RES>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc, res); break;
+        case 16: hipLaunchKernelGGL((pq_assign_kernel<16, VEC, RES>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc, res); break;
+        case 32: hipLaunchKernelGGL((pq_assign_kernel<32, VEC, RES>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc, res); break;
+        default: hipLaunchKernelGGL((pq_assign_kernel<64, VEC, RES>), grid, dim3(256), 0, st, X, ldx, n, shadow, hn, codes, ldc, res); break;
     }
 }
 
@@ -201,8 +230,28 @@ int cx_pq_assign(const uint16_t* X, long n, int d, long ldx, const uint16_t* sha
     const bool vec = (ldx % 8) == 0 && ((uintptr_t)X & 15) == 0;
     const long nblocks = (n + 255) / 256;
     const dim3 grid(m, (unsigned)min(nblocks, 65535L));
-    if (vec) launch_assign<true>(dsub, grid, (hipStream_t)stream, X, ldx, n, shadow, half_norm, codes, ldc);
-    else launch_assign<false>(dsub, grid, (hipStream_t)stream, X, ldx, n, shadow, half_norm, codes, ldc);
+    if (vec) launch_assign<true, false>(dsub, grid, (hipStream_t)stream, X, ldx, n, shadow, half_norm, codes, ldc);
+    else launch_assign<false, false>(dsub, grid, (hipStream_t)stream, X, ldx, n, shadow, half_norm, codes, ldc);
+    return done();
+}
+
+int cx_pq_assign_residual(const uint16_t* X, long n, int d, long ldx, const int32_t* labels, const uint16_t* centroids, int nlist,
+                          long ldcen, const uint16_t* shadow, const float* half_norm, int dsub, uint8_t* codes, long ldc,
+                          void* stream) {
+    if (n < 0 || nlist < 1 || !dsub_ok(d, dsub)) return CX_ERR_SHAPE;
+    if (n == 0) return CX_OK;
+    if (!X || !labels || !centroids || !shadow || !half_norm || !codes) return CX_ERR_ARG;
+    const int m = d / dsub;
+    if (ldx < d || ldc < m || ldcen < d || ((uintptr_t)X & 1) || ((uintptr_t)centroids & 1) || ((uintptr_t)labels & 3) ||
+        ((uintptr_t)shadow & 15) || ((uintptr_t)half_norm & 3))
+        return CX_ERR_ALIGN;
+    // eight elements per load where every sub-vector of the rows AND of the centroids is aligned for it
+    const bool vec = (ldx % 8) == 0 && ((uintptr_t)X & 15) == 0 && (ldcen % 8) == 0 && ((uintptr_t)centroids & 15) == 0;
+    const long nblocks = (n + 255) / 256;
+    const dim3 grid(m, (unsigned)min(nblocks, 65535L));
+    const ResidualSrc res = {labels, centroids, ldcen, nlist};
+    if (vec) launch_assign<true, true>(dsub, grid, (hipStream_t)stream, X, ldx, n, shadow, half_norm, codes, ldc, res);
+    else launch_assign<false, true>(dsub, grid, (hipStream_t)stream, X, ldx, n, shadow, half_norm, codes, ldc, res);
     return done();
 }
 

@@ -30,6 +30,10 @@
 //
 // cx_search_pq_topk is stage 1 over product-quantiser codes (search_pq_tiles_kernel, below the int8 kernel): the bf16 kernel
 // with the document panel gathered from a codebook by the tile's code bytes; everything else is shared as it is.
+//
+// cx_search_pq_window_topk is that walk with WIN = true (search_pq_window_kernel<BIAS>): the scan of an IVF index over PQ codes.
+// With BIAS every row also has an fp32 term added to each of its scores, once, after the K loop and before every test -- for
+// residual codes the score of (query, list centroid), which the coarse search already has.
 #include <type_traits>
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
@@ -218,8 +222,10 @@ CX_DEVICE void init_rows(const SearchParams& p, SearchLdsT<WIN>& L, int m0, int 
     }
 }
 
-// What fills the staging registers of the bf16 tile walk below.  RowStage: both panels from bf16 rows (stage).
+// What fills the staging registers of the bf16 tile walk below.  RowStage: both panels from bf16 rows (stage).  BIAS: whether
+// the stager also has a per-row term for the epilogue (begin_rows / row_bias: PqBiasStage); without one no addition exists.
 struct RowStage {
+    static constexpr bool BIAS = false;
     CX_DEVICE void begin_tile(const SearchParams&, int, int) const {}
     CX_DEVICE void operator()(const SearchParams& p, int m0, int n0, int k0, int tid, uint4 (&sq)[4], uint4 (&sd)[4]) const {
         stage(p, m0, n0, k0, tid, sq, sd);
@@ -238,6 +244,7 @@ CX_DEVICE void search_tiles_walk(const Params& p, Lds& L, const Stager& stager) 
     int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
     const int nk = p.d / BK;
 
+    if constexpr (Stager::BIAS) stager.begin_rows(p, m0, tid);   // (read in the epilogue, behind init_rows' barrier)
     init_rows<WIN>(p, L, m0, tid, t_begin, t_end);
 
     for (int t = t_begin; t < t_end; ++t) {
@@ -282,6 +289,14 @@ CX_DEVICE void search_tiles_walk(const Params& p, Lds& L, const Stager& stager) 
         for (int a = 0; a < 4; ++a) {
             const int row = wq * 64 + a * 16 + l15;
             const float thr = L.thr[row], bel = L.bel[row];
+            if constexpr (Stager::BIAS) {
+                // s = acc + bias, one addition per score: what is tested here and what insert_row reads from the tile
+                const float bs = stager.row_bias(row);
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[a][b][r] = fadd_single(acc[a][b][r], bs);
+            }
             bool h = false;
             if constexpr (WIN) {
                 const int nb = n0 + wd * 64 + 4 * lh;
@@ -480,8 +495,13 @@ struct PqParams : SearchParams {     // (D / ldd of the base stay unused)
     int flat;              // ldc == m and codes 16-B aligned: a tile's codes are one aligned run of bytes
 };
 
-struct PqSearchLds : SearchLds {
+template <bool WIN> struct PqSearchLdsT : SearchLdsT<WIN> {
     alignas(16) uint8_t code[TN * 128];   // [row of the tile][m]: the codes of the current corpus tile (m <= 128)
+};
+using PqSearchLds = PqSearchLdsT<false>;
+
+struct PqBiasSearchLds : PqSearchLdsT<true> {
+    float bias[TM];                       // the term added to every score of the row
 };
 
 // The tile's codes; row r >= N - n0 holds the codes of row N - 1 (read but never admitted, as the clamped rows of stage).
@@ -513,6 +533,7 @@ CX_DEVICE void stage_pq(const PqParams& p, const uint8_t* code, int m0, int k0, 
 // The stager of the PQ walk: the tile's codes go to LDS before the tile's first chunk (they were last read in the previous
 // tile's K loop, behind that tile's barriers), and every chunk's document half is gathered through them.
 struct PqStage {
+    static constexpr bool BIAS = false;
     uint8_t* code;
     CX_DEVICE void begin_tile(const PqParams& p, int n0, int tid) const {
         load_codes(p, code, n0, tid);
@@ -527,6 +548,32 @@ __global__ __launch_bounds__(256, 1) void search_pq_tiles_kernel(PqParams p) {
     extern __shared__ __attribute__((aligned(16))) char dsm[];
     PqSearchLds& L = *reinterpret_cast<PqSearchLds*>(dsm);
     search_tiles_walk<false>(p, L, PqStage{L.code});
+}
+
+// PqStage with a per-row term: bias[m] of the tile's rows sits in LDS next to thr / bel (a row past M reads row M - 1's and
+// is never admitted) and the walk's epilogue adds it to the row's sixteen accumulators per lane.
+struct PqBiasStage : PqStage {
+    static constexpr bool BIAS = true;
+    float* lbias;          // LDS, (TM)
+    const float* bias;     // (M)
+    CX_DEVICE void begin_rows(const PqParams& p, int m0, int tid) const {
+        if (tid < TM) lbias[tid] = bias[min(m0 + tid, p.M - 1)];
+    }
+    CX_DEVICE float row_bias(int row) const { return lbias[row]; }
+};
+
+// The windowed PQ scan: search_tiles_walk<true> (the band walk [t0, t1) in one piece, nsplit = 1) with the PQ stager.  A tile
+// starts at a multiple of 128 rows wherever the band starts, so load_codes' packed path applies as in the flat kernel.
+// BIAS = false has no bias array and no addition (not + 0.0f, which would turn -0 into +0).
+template <bool BIAS> __global__ __launch_bounds__(256, 1) void search_pq_window_kernel(PqParams p, const float* bias) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    if constexpr (BIAS) {
+        PqBiasSearchLds& L = *reinterpret_cast<PqBiasSearchLds*>(dsm);
+        search_tiles_walk<true>(p, L, PqBiasStage{{L.code}, L.bias, bias});
+    } else {
+        PqSearchLdsT<true>& L = *reinterpret_cast<PqSearchLdsT<true>*>(dsm);
+        search_tiles_walk<true>(p, L, PqStage{L.code});
+    }
 }
 
 constexpr int MAXLISTS = 256;       // lists merged into one output row (>= MAXSPLIT)
@@ -823,6 +870,56 @@ int cx_search_int8_window_topk(const int8_t* Q, const int8_t* D, const float* q_
         if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel<true>), (int)sizeof(Int8SearchLds<true>)))
             return CX_ERR_LAUNCH;
         hipLaunchKernelGGL(search_int8_tiles_kernel<true>, dim3((M + TM - 1) / TM), dim3(256), sizeof(Int8SearchLds<true>), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    // the row's one list, padded, in the output layout
+    const SplitLists S = {lists, counts, 1, k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? 1 : 0, k, out_scores,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_search_pq_window_ws_bytes(int M, int k) { return cx_search_window_ws_bytes(M, k); }
+
+int cx_search_pq_window_topk(const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int M, long N, int d, int dsub,
+                             long ldq, long ldc, int k, const int64_t* min_id, const int64_t* end_id, const float* bias,
+                             const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
+                             float* out_scores, int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (dsub != 8 && dsub != 16 && dsub != 32 && dsub != 64) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Q || !out_scores || !out_ids || (N > 0 && (!codes || !codebook || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
+    const int m = d / dsub;
+    if (ldq < d || (ldq % 8) != 0 || (N > 0 && ldc < m)) return CX_ERR_ALIGN;
+    if (((uintptr_t)Q & 15) || ((uintptr_t)codebook & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)bias & 3)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    Cand* lists = reinterpret_cast<Cand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
+    if (N > 0) {
+        PqParams p = {};
+        p.Q = Q; p.ldq = ldq;
+        p.codes = codes; p.cb = codebook; p.ldc = ldc; p.m = m;
+        p.lsub = dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6;
+        p.flat = (ldc == m && ((uintptr_t)codes & 15) == 0) ? 1 : 0;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = 1;   // one workgroup walks a query tile's whole band
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = p.tiles_n;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
+        p.min_id = min_id; p.end_id = end_id;
+        p.lists = lists; p.counts = counts;
+        const dim3 grid((M + TM - 1) / TM);
+        if (bias) {
+            static CxLdsOptIn opt;
+            if (!opt.ensure(reinterpret_cast<const void*>(&search_pq_window_kernel<true>), (int)sizeof(PqBiasSearchLds)))
+                return CX_ERR_LAUNCH;
+            hipLaunchKernelGGL(search_pq_window_kernel<true>, grid, dim3(256), sizeof(PqBiasSearchLds), s, p, bias);
+        } else {
+            static CxLdsOptIn opt;
+            if (!opt.ensure(reinterpret_cast<const void*>(&search_pq_window_kernel<false>), (int)sizeof(PqSearchLdsT<true>)))
+                return CX_ERR_LAUNCH;
+            hipLaunchKernelGGL(search_pq_window_kernel<false>, grid, dim3(256), sizeof(PqSearchLdsT<true>), s, p, bias);
+        }
         if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
     }
     // the row's one list, padded, in the output layout

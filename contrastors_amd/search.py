@@ -540,10 +540,10 @@ class _IVFLists:
         self._coarse = FlatIPIndex(self.d, device=self.device, workspace_bytes=self.workspace_bytes)
         self._coarse.add(c)
 
-    def _append(self, cols: tuple, xb: torch.Tensor) -> None:
-        """One chunk of rows: cols is what the index keeps of them, xb (n, d) their bf16 roundings on the device.  Every row is
-        labelled with the list of its largest inner product over the centroids' bf16 roundings, ties to the lower list
-        (cx_kmeans_assign without a bias): the first probe the coarse search returns for the same vector."""
+    def _label(self, xb: torch.Tensor) -> torch.Tensor:
+        """xb (n, d) contiguous bf16 rows on the device -> (n,) int32: every row's list, the one of its largest inner product
+        over the centroids' bf16 roundings, ties to the lower list (cx_kmeans_assign without a bias): the first probe the coarse
+        search returns for the same vector."""
         n = xb.shape[0]
         labels = torch.empty(n, dtype=torch.int32, device=self.device)
         best = torch.empty(n, dtype=torch.float32, device=self.device)
@@ -551,8 +551,17 @@ class _IVFLists:
         with torch.cuda.device(self.device):
             _C.check(_C.lib().cx_kmeans_assign(xb.data_ptr(), C.data_ptr(), None, n, self.nlist, self.d, self.d, self.d,
                                                labels.data_ptr(), best.data_ptr(), None, _C.cur_stream()), "cx_kmeans_assign")
+        return labels
+
+    def _push(self, cols: tuple, labels: torch.Tensor) -> None:
+        """One labelled chunk of rows: cols is what the index keeps of them."""
         self._pending.append((cols, labels))
-        self.ntotal += n
+        self.ntotal += labels.shape[0]
+
+    def _append(self, cols: tuple, xb: torch.Tensor) -> None:
+        """One chunk of rows: cols is what the index keeps of them, xb (n, d) their bf16 roundings on the device, from which
+        they are labelled (_label)."""
+        self._push(cols, self._label(xb))
 
     def _finalise(self) -> None:
         """Sort what was added since the last search into the lists.  The sorted rows and the new chunks are concatenated
@@ -618,7 +627,12 @@ class _IVFLists:
         """-> (the queries rounded to bf16 on the device, for the coarse probe; what _scan gathers its pair rows from)."""
         raise NotImplementedError
 
-    def _scan(self, h, prepared, b0: int, m: int, pair_q, k: int, mid, end, pptr, pids, bg, ws, ls, li, stream) -> None:
+    def _pair_bias(self, coarse_scores: torch.Tensor, src: torch.Tensor) -> Optional[torch.Tensor]:
+        """coarse_scores (m, nprobe): the coarse search's score of (query, probed list); src: ivf_pair_plan's.  -> (P,) float32,
+        a term the scan adds to every score of a pair row, or None (no such term: the scores of the stored rows stand alone)."""
+        return None
+
+    def _scan(self, h, prepared, b0: int, m: int, pair_q, k: int, mid, end, pptr, pids, bg, bias, ws, ls, li, stream) -> None:
         """One windowed top-k launch over the pair rows of queries [b0, b0 + m): lists into (ls, li)."""
         raise NotImplementedError
 
@@ -646,7 +660,7 @@ class _IVFLists:
             h = _C.lib()
             with torch.cuda.device(self.device):
                 stream = _C.cur_stream()
-                probes = self._coarse.search(q, nprobe)[1]
+                coarse, probes = self._coarse.search(q, nprobe)
                 dptr = xids = None
                 if row_ptr is not None and xhost.numel():
                     dptr, xids = row_ptr.to(self.device), xhost.to(self.device)
@@ -664,7 +678,8 @@ class _IVFLists:
                     ws = torch.empty(h.cx_search_window_ws_bytes(P, k), dtype=torch.uint8, device=self.device)
                     ls = torch.empty(P, k, dtype=torch.float32, device=self.device)
                     li = torch.empty(P, k, dtype=torch.int64, device=self.device)
-                    self._scan(h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, ws, ls, li, stream)
+                    bias = self._pair_bias(coarse[b0: b0 + m], src)
+                    self._scan(h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, bias, ws, ls, li, stream)
                     _C.check(h.cx_topk_merge_lists(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
                                                    self._order.data_ptr(), self.ntotal, scores[b0].data_ptr(),
                                                    ids[b0].data_ptr(), stream), "cx_topk_merge_lists")
@@ -685,8 +700,8 @@ class IVFFlatIndex(_IVFLists):
     and maps positions back to original ids.  No per-list launches; nothing but sizes is read back.
 
     The sort happens at the first search after an add and needs, at its peak, twice the corpus in device memory (the old
-    rows and their gathered copy).  Not here: L2, residual / PQ codes (int8 codes with one scale per row: IVFInt8Index), host
-    rows, save / load (centroids go in and out as arrays), incremental adds without a re-sort."""
+    rows and their gathered copy).  Not here: L2 (int8 codes with one scale per row: IVFInt8Index; PQ codes of the residuals:
+    IVFPQIndex), host rows, save / load (centroids go in and out as arrays), incremental adds without a re-sort."""
 
     _ENTRY = "cx_search_window_topk"
 
@@ -717,7 +732,7 @@ class IVFFlatIndex(_IVFLists):
         q = _to_device_2d(queries, self.d, self.device)
         return q, q
 
-    def _scan(self, h, q, b0, m, pair_q, k, mid, end, pptr, pids, bg, ws, ls, li, stream) -> None:
+    def _scan(self, h, q, b0, m, pair_q, k, mid, end, pptr, pids, bg, bias, ws, ls, li, stream) -> None:
         qg = q[b0: b0 + m][pair_q]
         _C.check(h.cx_search_window_topk(qg.data_ptr(), self._rows.data_ptr(), pair_q.numel(), self.ntotal, self.d,
                                          self.d, self.d, k, mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
@@ -1337,7 +1352,7 @@ class IVFInt8Index(_IVFLists):
             _quantize_rows_device(part, qc[r0:r1], qs[r0:r1])
         return qb, (qc, qs)
 
-    def _scan(self, h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, ws, ls, li, stream) -> None:
+    def _scan(self, h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, bias, ws, ls, li, stream) -> None:
         qc, qs = prepared
         cg, sg = qc[b0: b0 + m][pair_q], qs[b0: b0 + m][pair_q]
         D, ds = self._cols
@@ -1519,7 +1534,7 @@ class PQFlatIndex:
     codebook in LDS-staging order, so `search` equals `FlatIPIndex.search` over `decode()` bit for bit.  Same surface as
     FlatIPIndex / Int8FlatIndex; search_pq_rescored re-scores its candidates exactly against the float rows.
 
-    Not here: IVF lists and residual encoding, OPQ rotations, other code widths, a look-up-table scan, save / load (codebooks go
+    Not here (IVF lists and residual encoding: IVFPQIndex): OPQ rotations, other code widths, a look-up-table scan, save / load (codebooks go
     in and out as arrays), more than one GPU."""
 
     def __init__(self, d: int, dsub: int = 8, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
@@ -1670,6 +1685,11 @@ class PQFlatIndex:
             if ids.dim() != 1 or (ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal)):
                 raise ValueError(f"decode: expected a 1-d list of ids in [0, {self.ntotal})")
             codes = codes[ids]
+        return self.decode_codes(codes)
+
+    def decode_codes(self, codes: torch.Tensor) -> torch.Tensor:
+        """(n, m) uint8 codes on the device -> (n, d) bf16: the concatenation of codebooks[s][codes[n][s]]."""
+        self._require_trained()
         s = torch.arange(self.m, device=self.device)[None, :]
         return self._shadow[s, codes.to(torch.int64)].reshape(codes.shape[0], self.d)
 
@@ -1752,6 +1772,195 @@ def search_pq_rescored(index: PQFlatIndex, vectors, queries, k: int, rescore_fac
     index._require_trained()
     qd = _to_device_2d(queries, index.d, index.device)
     cand = _paged_candidates(lambda kp, ex: index.search(qd, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+
+
+class IVFPQIndex(_IVFLists):
+    """Inverted-file index over product-quantised residuals on one GPU (faiss IndexIVFPQ, 8 bits per sub-quantiser, inner
+    product): IVFFlatIndex's lists -- the same centroids and rows give the same lists -- holding d / dsub bytes per row.  With
+    by_residual (the default) a row is encoded as its residual to its list's centroid, r = bf16(x - c_l), so the 256 centroids
+    of a sub-quantiser cover one list's spread and not the corpus; the score of (q, n) is q . decode(code_n) + q . c_l, and
+    q . c_l is the score the coarse search already returned for the probe.  One cx_search_pq_window_topk launch per query batch
+    over the (query, probed list) pairs -- the windowed walk of IVFFlatIndex with PQFlatIndex's gathered document panel and the
+    coarse score added per pair row in the epilogue -- and one cx_topk_merge_lists call.  tests/ivf_pq_ref.py is the contract.
+    by_residual=False stores PQFlatIndex's codes of the rows themselves and adds nothing: probing every list then returns
+    PQFlatIndex.search's result with the same codebooks, bit for bit.  search_ivf_pq_rescored re-scores the candidates exactly.
+
+    `pq` is the PQFlatIndex that holds the codebooks (it stores no rows).  Not here: OPQ rotations, other code widths, a
+    look-up-table scan, adding (codes, labels) made elsewhere, save / load (centroids and codebooks go in and out as arrays),
+    more than one GPU."""
+
+    _ENTRY = "cx_search_pq_window_topk"
+
+    def __init__(self, d: int, nlist: int, dsub: int = 8, by_residual: bool = True, device="cuda",
+                 workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
+        self.m = _check_pq_dims(int(d), int(dsub))
+        super().__init__(d, nlist, device=device, workspace_bytes=workspace_bytes, seed=seed)
+        self.dsub = int(dsub)
+        self.by_residual = bool(by_residual)
+        self.pq = PQFlatIndex(self.d, self.dsub, device=self.device, workspace_bytes=self.workspace_bytes, seed=self.seed)
+
+    @property
+    def is_trained(self) -> bool:
+        return self._centroids is not None and self.pq.is_trained
+
+    def _require_trained(self) -> None:
+        super()._require_trained()
+        self.pq._require_trained()
+
+    def _residuals(self, xb: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """bf16 rows and their lists -> the bf16 residuals, the contract's arithmetic in torch ops: one fp32 subtraction and
+        one rounding to nearest even per element."""
+        return (xb.float() - self._coarse.vectors[labels.to(torch.int64)].float()).to(torch.bfloat16)
+
+    def train(self, x=None, max_iter: int = 25, sample: Optional[int] = None, centroids=None, codebooks=None, pq_iters: int = 25,
+              pq_sample: Optional[int] = None) -> None:
+        """The coarse fit of the base class (x with max_iter / sample, or centroids= as they are), then the codebooks: given
+        codebooks= (m, 256, dsub) are taken as they are; otherwise PQFlatIndex.train (pq_iters Lloyd steps, seeded) on the
+        residuals of the rows pq_train_rows chooses from x (pq_sample rows, default min(n, 65 536)) to the centroids of their
+        lists -- on the rows themselves without by_residual.  The same x and seed give the same bits."""
+        if x is None and (centroids is None or codebooks is None):
+            raise ValueError("train: give the training rows, or both centroids= and codebooks=")
+        if self.ntotal:
+            raise RuntimeError("train: the index holds rows encoded with the current centroids and codebooks; reset() first")
+        if x is not None and (len(np.shape(x)) != 2 or np.shape(x)[1] != self.d):
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(x))}")
+        if centroids is not None and tuple(np.shape(centroids)) != (self.nlist, self.d):
+            raise ValueError(f"expected ({self.nlist}, {self.d}) centroids, got shape {tuple(np.shape(centroids))}")
+        ns = 0
+        if codebooks is not None:
+            _check_codebooks(codebooks, self.d, self.dsub)
+        else:
+            n = int(np.shape(x)[0])
+            if int(pq_iters) < 0:
+                raise ValueError(f"pq_iters must not be negative, got {pq_iters}")
+            if pq_sample is not None and not PQ_KSUB <= int(pq_sample) <= PQ_MAX_SAMPLE:
+                raise ValueError(f"pq_sample must be in [{PQ_KSUB}, {PQ_MAX_SAMPLE}], got {pq_sample}")
+            ns = min(n, PQ_DEFAULT_SAMPLE if pq_sample is None else int(pq_sample))
+            if ns < PQ_KSUB:
+                raise ValueError(f"train: {PQ_KSUB} centroids need at least {PQ_KSUB} rows, got {ns}")
+        super().train(None if centroids is not None else x, max_iter=max_iter, sample=sample, centroids=centroids)
+        if codebooks is not None:
+            self.pq.train(codebooks=codebooks)
+            return
+        rows, _ = pq_train_rows(n, ns, self.seed)
+        if rows is None:
+            xs = x
+        elif isinstance(x, torch.Tensor):
+            xs = x[rows.to(x.device)]
+        else:
+            xs = x[rows.numpy()]
+        xs = xs if isinstance(xs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(xs, dtype=np.float32)))
+        xb = xs.to(self.device).to(torch.bfloat16).contiguous()
+        if self.by_residual:
+            xb = self._residuals(xb, self._label(xb))
+        # the sample is chosen: PQFlatIndex.train takes all ns rows and starts from the same 256 of them
+        self.pq.train(xb, max_iter=int(pq_iters), sample=ns)
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """The stored codes in list order, (ntotal, m) uint8 (a view): row p is the row add() gave the id _order[p]."""
+        self._finalise()
+        if self._cols is None:
+            return torch.empty(0, self.m, dtype=torch.uint8, device=self.device)
+        return self._cols[0]
+
+    def add(self, x) -> None:
+        """Append float rows (a tensor anywhere, an array or a memmap); row i of the n-th add gets id ntotal + i.  The rows go
+        through the device QUANTIZE_ROWS at a time: each chunk is rounded to bf16 as FlatIPIndex.add rounds it, labelled exactly
+        as IVFFlatIndex.add labels it and encoded -- cx_pq_assign_residual forms every row's residual to its list's centroid in
+        registers (cx_pq_assign on the rows themselves without by_residual); only the codes and the labels stay."""
+        self._require_trained()
+        n = self._check_queries(x)
+        if self.ntotal + n > MAX_NTOTAL:
+            raise ValueError(f"IVFPQIndex holds at most {MAX_NTOTAL} vectors")
+        h = _C.lib()
+        C = self._coarse.vectors
+        for r0, r1, part in _float_chunks(x, n, self.device):
+            xb = part.to(torch.bfloat16).contiguous()
+            labels = self._label(xb)
+            codes = torch.empty(r1 - r0, self.m, dtype=torch.uint8, device=self.device)
+            if self.by_residual:
+                with torch.cuda.device(self.device):
+                    _C.check(h.cx_pq_assign_residual(xb.data_ptr(), r1 - r0, self.d, self.d, labels.data_ptr(), C.data_ptr(),
+                                                     self.nlist, self.d, self.pq._shadow.data_ptr(), self.pq._hn.data_ptr(),
+                                                     self.dsub, codes.data_ptr(), self.m, _C.cur_stream()),
+                             "cx_pq_assign_residual")
+            else:
+                _pq_assign_device(xb, self.pq._shadow, self.pq._hn, codes)
+            self._push((codes,), labels)
+
+    def decode(self, ids=None) -> torch.Tensor:
+        """-> (n, d) fp32: what the stored codes stand for, for all rows in add() order or for the given ids -- the list's bf16
+        centroid plus the decoded residual (one fp32 addition per element), or the decoded row without by_residual."""
+        self._require_trained()
+        if ids is None:
+            ids = torch.arange(self.ntotal, dtype=torch.int64, device=self.device)
+        else:
+            ids = torch.as_tensor(ids if isinstance(ids, torch.Tensor) else np.asarray(ids)).to(device=self.device, dtype=torch.int64)
+            if ids.dim() != 1 or (ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.ntotal)):
+                raise ValueError(f"decode: expected a 1-d list of ids in [0, {self.ntotal})")
+        if not ids.numel():
+            return torch.empty(0, self.d, dtype=torch.float32, device=self.device)
+        self._finalise()
+        pos = self._inv[ids]
+        out = self.pq.decode_codes(self._cols[0][pos]).float()
+        if self.by_residual:
+            out += self._coarse.vectors[self._labels[pos].to(torch.int64)].float()
+        return out
+
+    def _pair_row_bytes(self) -> int:
+        return 2 * self.d + 4
+
+    def _prepare_queries(self, queries):
+        q = _to_device_2d(queries, self.d, self.device)
+        return q, q
+
+    def _pair_bias(self, coarse_scores, src):
+        if not self.by_residual:
+            return None
+        bias = torch.empty(src.numel(), dtype=torch.float32, device=self.device)
+        bias[src.view(-1)] = coarse_scores.reshape(-1)
+        return bias
+
+    def _scan(self, h, q, b0, m, pair_q, k, mid, end, pptr, pids, bg, bias, ws, ls, li, stream) -> None:
+        qg = q[b0: b0 + m][pair_q]
+        _C.check(h.cx_search_pq_window_topk(qg.data_ptr(), self._cols[0].data_ptr(), self.pq._shadow.data_ptr(), pair_q.numel(),
+                                            self.ntotal, self.d, self.dsub, self.d, self.m, k, mid.data_ptr(), end.data_ptr(),
+                                            _C.ptr(bias), _C.ptr(pptr), _C.ptr(pids), _C.ptr(bg), ws.data_ptr(), ls.data_ptr(),
+                                            li.data_ptr(), stream), "cx_search_pq_window_topk")
+
+    def search(self, queries, k: int, nprobe: int, exclude=None, below=None):
+        """-> (scores (M, k) float32, ids (M, k) int64), the conventions of FlatIPIndex.search (descending score, ties to the
+        lower id, (-inf, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows of
+        the nprobe lists nearest to each query, 1 <= nprobe <= min(nlist, 256).  The score of a row of list l is
+        fp32(acc + coarse), acc with the bits FlatIPIndex.search gives (q, the decoded code) and coarse the coarse search's
+        score of (q, c_l); acc alone without by_residual.  ids, and the ids of exclude, are the ids add() gave; below is a
+        strict bound on that score."""
+        return super().search(queries, k, nprobe, exclude=exclude, below=below)
+
+
+def search_ivf_pq_rescored(index: IVFPQIndex, vectors, queries, k: int, nprobe: int, rescore_factor: int = 4, exclude=None,
+                           below=None):
+    """search_pq_rescored over an IVFPQIndex: the min(k * rescore_factor, 4096) best PQ scores among the rows of the nprobe
+    lists nearest to each query, then the k best of those by exact inner product with `vectors` (the corpus the index was made
+    from, in add() order: device bf16 rows, a host array or a memmap; see rescore).  queries: float rows.  exclude applies to
+    the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit when every
+    list is probed and the candidate lists cover the corpus."""
+    k, nprobe = int(k), int(nprobe)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    if not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
+        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
+    index._require_trained()
+    as_numpy = not isinstance(queries, torch.Tensor)
+    M = index._check_queries(queries)
+    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
+    if below is not None:
+        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
+        if n_below != M:
+            raise ValueError(f"below has {n_below} entries for {M} queries")
+    qd = _to_device_2d(queries, index.d, index.device)
+    cand = _paged_candidates(lambda kp, ex: index.search(qd, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
     return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
 
 

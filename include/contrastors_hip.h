@@ -574,6 +574,29 @@ long cx_search_pq_ws_bytes(int M, long N, int k, int nsplit);
 int cx_search_pq_topk(const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int M, long N, int d, int dsub,
                       long ldq, long ldc, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
                       int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream);
+/* ---- IVF over product-quantised residuals (faiss IndexIVFPQ, inner product; csrc/pq.hip, csrc/search.hip).  Additive:
+ *          cx_abi_version stays 10.  tests/ivf_pq_ref.py is the contract. -------------------------------------------------
+ * cx_pq_assign_residual: cx_pq_assign over the residual of every row to the centroid of its list.  labels:(n) int32, 4-B
+ * aligned; centroids:(nlist,d) bf16, leading dimension ldcen ELEMENTS >= d, nlist >= 1 (CX_ERR_SHAPE).  r_j =
+ * bf16(f32(x_j) - f32(centroids[labels[i]][j])): one fp32 subtraction and one rounding to nearest even per element, formed in
+ * registers (the residuals are never stored); the codes are cx_pq_assign's of r.  A label is clamped into [0, nlist) for the
+ * read, so no label reads outside the table; the code of such a row is unspecified.  Other operands, refusals, n == 0: as
+ * cx_pq_assign.
+ * cx_search_pq_window_topk: cx_search_pq_topk's operands, alignment rules and refusals with cx_search_window_topk's window
+ * (min_id / end_id, the band walk in one workgroup, ids reported as positions, M == 0 and N == 0 as there) and an optional
+ * bias:(M) fp32, 4-B aligned.  The score of (m, n) is s = acc + bias[m]: acc has the bits cx_search_topk gives query m and the
+ * decoded row n, and the sum is one fp32 addition after the K loop; below, the order (s descending, id ascending), the
+ * exclusions and the (-inf, -1) padding act on s.  bias == NULL: no addition at all (s = acc, -0 stays -0), which is
+ * cx_search_window_topk over the decoded rows bit for bit.  ws: 16-B aligned, cx_search_pq_window_ws_bytes(M, k)
+ * (== cx_search_window_ws_bytes(M, k)) bytes, need not be initialised. */
+int cx_pq_assign_residual(const uint16_t* X, long n, int d, long ldx, const int32_t* labels, const uint16_t* centroids, int nlist,
+                          long ldcen, const uint16_t* shadow, const float* half_norm, int dsub, uint8_t* codes, long ldc,
+                          void* stream);
+long cx_search_pq_window_ws_bytes(int M, int k);
+int cx_search_pq_window_topk(const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int M, long N, int d, int dsub,
+                             long ldq, long ldc, int k, const int64_t* min_id, const int64_t* end_id, const float* bias,
+                             const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
+                             float* out_scores, int64_t* out_ids, void* stream);
 /* backward of  coef * sum_i loss_rows[i]:  Gm[i][j] = coef*scale*(softmax_ij - [j==label_i]) is written to
  * Gmat:(N,G) and GmatT:(G,N) fp32 scratch; dQ:(N,dim) = Gm D, dD:(G,dim) = Gm^T Q (overwritten);
  * dscale_accum (may be NULL): += coef * sum_ij (softmax_ij - y_ij) * (Q D^T)_ij   (d loss / d scale).
