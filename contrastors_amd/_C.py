@@ -202,6 +202,11 @@ _SIGS = {
     "cx_pack_sign_bits": (i32, [vp, i32, i64, i32, i64, vp, i64, vp]),
     "cx_search_hamming_ws_bytes": (i64, [i32, i64, i32, i32]),
     "cx_search_hamming_topk": (i32, [vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "cx_search_hamming_window_ws_bytes": (i64, [i32, i32]),
+    "cx_search_hamming_window_topk": (i32, [vp, vp, i32, i64, i32, i64, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "cx_hamming_merge_lists": (i32, [vp, vp, i64, i32, vp, i32, i32, vp, i64, vp, vp, vp]),
+    "cx_binary_kmeans_update_ws_bytes": (i64, [i64, i32, i32]),
+    "cx_binary_kmeans_update": (i32, [vp, i64, i32, i64, vp, i32, vp, vp, vp, vp]),
     "cx_rescore_topk": (i32, [vp, vp, vp, vp, i32, i64, i32, i64, i64, i32, i32, vp, vp, vp, vp]),
     "cx_quantize_rows_int8": (i32, [vp, i32, i64, i32, i64, vp, i64, vp, vp]),
     "cx_search_int8_ws_bytes": (i64, [i32, i64, i32, i32]),

@@ -21,10 +21,15 @@
 // split count.  Integer distances tie all the time: an entry equal to a full list's k-th distance cannot enter (its id is
 // larger: ids grow along a split, and the candidates of one tile are ranked together before they meet the list), and the
 // split merge ranks by (distance, id).  No atomics; the (M, N) distances are never written.
+//
+// cx_search_hamming_window_topk is that walk with a per-row id window (hamming_tiles_walk<true>): the scan of an IVF index over
+// sign codes (IVFBinaryIndex), whose (query, list) pair rows cx_hamming_merge_lists merges per query and whose coarse
+// quantiser is trained in the code domain by cx_binary_kmeans_update (k-majority; integer atomics only).
 #include "cx_common.h"
 #include "../../include/contrastors_hip.h"
 
 #include <limits.h>
+#include <type_traits>
 
 namespace {
 
@@ -65,6 +70,12 @@ struct HammingParams {
     const int32_t* maxd;   // (M) inclusive upper bound on the distance, or null
     HCand* lists;          // (M, nsplit, k)
     int* counts;           // (M, nsplit)
+};
+
+// cx_search_hamming_window_topk: row m also has an id window min_id[m] < n < end_id[m] (nsplit = 1)
+struct WinHammingParams : HammingParams {
+    const int64_t* min_id; // (M) exclusive lower id bound, or null (= -1 everywhere)
+    const int64_t* end_id; // (M) exclusive upper id bound, or null (= N everywhere)
 };
 
 // thread tid stages 128 code bits of one row: query row tid (tid < 128) or document row tid - 128
@@ -115,6 +126,14 @@ struct HammingLds {
     int any;
 };
 
+struct WinHammingLds : HammingLds {
+    int mid[TM], end[TM];         // min_id clamped to [-1, N], end_id clamped to [0, N]
+    int minmid, maxend;           // over the tile's rows with a non-empty window
+};
+
+template <bool WIN> using HammingLdsT = typename std::conditional<WIN, WinHammingLds, HammingLds>::type;
+template <bool WIN> using HammingParamsT = typename std::conditional<WIN, WinHammingParams, HammingParams>::type;
+
 CX_DEVICE int acc_of_dist(int d, int dist) { return UNIT * (d - 2 * dist); }
 
 // one wave: merge the c candidates in L.cand[wave] into the row's running list (rank counting), refresh its threshold
@@ -156,9 +175,11 @@ CX_DEVICE void merge_row(const HammingParams& p, HammingLds& L, int row, int m, 
 // one wave: the admissible entries of tile row `row` join the row's pending candidates; a merge into the list in global
 // memory (a chain of dependent loads) happens only when they no longer fit.  Between merges the row's threshold is the k-th
 // distance of an OLDER list: it admits more than the current one would, never less, and what it admits wrongly ranks past k in
-// the next merge.
-CX_DEVICE void insert_row(const HammingParams& p, HammingLds& L, const int* tile, int row, int m, int n0, int split, int wave,
-                          int lane) {
+// the next merge.  WIN: the row's id window is one more admission test; ids still ascend along the (single) walk, so the
+// argument stands as it is.
+template <bool WIN>
+CX_DEVICE void insert_row(const HammingParams& p, HammingLdsT<WIN>& L, const int* tile, int row, int m, int n0, int split,
+                          int wave, int lane) {
     const int thr = L.thr[row], bel = L.bel[row], pc = L.pcnt[row];
     const int64_t x0 = p.xptr ? p.xptr[m] : 0, x1 = p.xptr ? p.xptr[m + 1] : 0;
     bool ok[2];
@@ -169,6 +190,7 @@ CX_DEVICE void insert_row(const HammingParams& p, HammingLds& L, const int* tile
         const int j = lane + 64 * h, n = n0 + j;
         const int a = tile[row * TN + j];
         ok[h] = n < p.N && a > thr && a >= bel;
+        if constexpr (WIN) ok[h] = ok[h] && n > L.mid[row] && n < L.end[row];
         if (ok[h])
             for (int64_t x = x0; x < x1; ++x)
                 if (p.xids[x] == n) ok[h] = false;
@@ -195,19 +217,42 @@ CX_DEVICE void insert_row(const HammingParams& p, HammingLds& L, const int* tile
     merge_row(p, L, row, m, split, wave, lane, c + pc);
 }
 
-__global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) {
-    extern __shared__ __attribute__((aligned(16))) char dsm[];
-    HammingLds& L = *reinterpret_cast<HammingLds*>(dsm);
+// The walk of one (query tile, split) workgroup over its corpus tiles: the body of hamming_tiles_kernel (WIN = false) and of
+// hamming_window_kernel (WIN = true), which is to it what search_tiles_kernel<true> is to search_tiles_kernel<false>: per-row
+// windows clamped as init_rows<true> clamps them, kept next to thr / bel, tested in the register epilogue and in insert_row;
+// the walk covers the band [t0, t1) of the tile's non-empty windows in one piece (nsplit = 1), nothing for a tile without one.
+template <bool WIN> CX_DEVICE void hamming_tiles_walk(const HammingParamsT<WIN>& p, HammingLdsT<WIN>& L) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wq = wave >> 1, wd = wave & 1, l15 = lane & 15, lh = lane >> 4;
     const int tm = blockIdx.x / p.nsplit, split = blockIdx.x % p.nsplit;
     const int m0 = tm * TM;
-    const int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
+    int t_begin = split * p.tiles_per_split, t_end = min(p.tiles_n, t_begin + p.tiles_per_split);
     const int nk = (p.d + BKD - 1) / BKD;
 
+    if constexpr (WIN) {
+        if (tid == 0) { L.minmid = INT_MAX; L.maxend = 0; }
+        __syncthreads();
+    }
     if (tid < TM) {
         const int m = m0 + tid;
-        L.thr[tid] = m < p.M ? INT_MIN : INT_MAX;   // rows past M never pass the threshold test
+        bool live = m < p.M;   // rows past M never pass the threshold test
+        if constexpr (WIN) {
+            int id = -1, e = 0;
+            if (live) {
+                const int64_t v = p.min_id ? p.min_id[m] : (int64_t)-1;
+                const int64_t w = p.end_id ? p.end_id[m] : (int64_t)p.N;
+                id = (int)min(max(v, (int64_t)-1), (int64_t)p.N);
+                e = (int)min(max(w, (int64_t)0), (int64_t)p.N);
+                live = e > id + 1;   // ... nor do rows with an empty window, which stay out of the walk's bounds
+                if (live) {
+                    atomicMin(&L.minmid, id);   // (LDS)
+                    atomicMax(&L.maxend, e);
+                }
+            }
+            L.mid[tid] = id;
+            L.end[tid] = e;
+        }
+        L.thr[tid] = live ? INT_MIN : INT_MAX;
         int bel = INT_MIN;
         if (m < p.M && p.maxd) {
             const int md = p.maxd[m];
@@ -220,6 +265,11 @@ __global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) 
     }
     if (tid == 0) L.any = 0;
     __syncthreads();
+    if constexpr (WIN) {
+        // a non-empty row has mid + 1 < end <= N: t_begin < t_end <= tiles_n; a tile of empty windows walks nothing
+        t_begin = L.maxend > 0 ? (L.minmid + 1) / TN : 0;
+        t_end = L.maxend > 0 ? (L.maxend + TN - 1) / TN : 0;
+    }
 
     for (int t = t_begin; t < t_end; ++t) {
         const int n0 = t * TN;
@@ -263,13 +313,25 @@ __global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) 
             const int row = wq * 64 + a * 16 + l15;
             const int thr = L.thr[row], bel = L.bel[row];
             bool h = false;
+            if constexpr (WIN) {
+                const int nb = n0 + wd * 64 + 4 * lh;
+                const int lim = L.mid[row] - nb, top = L.end[row] - nb;   // column nb + c is inside the window  <=>  lim < c < top
 #pragma unroll
-            for (int b = 0; b < 4; ++b)
+                for (int b = 0; b < 4; ++b)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int v = acc[a][b][r];
-                    h |= (v > thr) & (v >= bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
-                }
+                    for (int r = 0; r < 4; ++r) {
+                        const int v = acc[a][b][r];
+                        h |= (v > thr) & (v >= bel) & (b * 16 + r > lim) & (b * 16 + r < top);   // (end <= N)
+                    }
+            } else {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int v = acc[a][b][r];
+                        h |= (v > thr) & (v >= bel) & (n0 + wd * 64 + b * 16 + 4 * lh + r < p.N);
+                    }
+            }
             if (h) L.flag[row] = 1;
             hit |= h;
         }
@@ -288,7 +350,7 @@ __global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) 
             while (todo) {
                 const int row = wave + 4 * (__ffsll(todo) - 1);
                 todo &= todo - 1;
-                insert_row(p, L, tile, row, m0 + row, n0, split, wave, lane);
+                insert_row<WIN>(p, L, tile, row, m0 + row, n0, split, wave, lane);
             }
             __syncthreads();
             if (tid < TM) L.flag[tid] = 0;
@@ -296,7 +358,8 @@ __global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) 
         }
         __syncthreads();
     }
-    // what is still pending goes into the lists
+    // what is still pending goes into the lists (nothing is for a tile that walked nothing and for rows past M: they admit
+    // no candidate, so their pcnt is the 0 it started as)
     for (int row = wave; row < TM; row += 4) {
         const int pc = L.pcnt[row];
         if (pc == 0) continue;
@@ -306,6 +369,16 @@ __global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) 
     }
     __syncthreads();
     if (tid < TM && m0 + tid < p.M) p.counts[(int64_t)(m0 + tid) * p.nsplit + split] = L.cnt[tid];
+}
+
+__global__ __launch_bounds__(256, 1) void hamming_tiles_kernel(HammingParams p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    hamming_tiles_walk<false>(p, *reinterpret_cast<HammingLds*>(dsm));
+}
+
+__global__ __launch_bounds__(256, 1) void hamming_window_kernel(WinHammingParams p) {
+    extern __shared__ __attribute__((aligned(16))) char dsm[];
+    hamming_tiles_walk<true>(p, *reinterpret_cast<WinHammingLds*>(dsm));
 }
 
 // one wave per query row: merge the row's nsplit sorted lists into its top-k
@@ -334,6 +407,213 @@ __global__ __launch_bounds__(256) void hamming_merge_kernel(const HCand* __restr
     for (int r = min(total, k) + lane; r < k; r += 64) {
         out_d[(int64_t)row * k + r] = INT_MAX;
         out_id[(int64_t)row * k + r] = -1;
+    }
+}
+
+// ---- the per-query merge of an IVF search over sign codes -----------------------------------------------------------------
+constexpr int MAXLISTS = 256;       // lists merged into one output row
+
+// (P, k) distance / id arrays as the Hamming entry points write them: sorted rows padded with (INT32_MAX, -1), so a list ends
+// at its first negative id.  Output row m merges the lists src[m][0 .. L); an entry outside [0, P) names no list.  id_map (or
+// null): the reported id of position n is id_map[n], n clamped to [0, N) for the read.
+struct HammingLists {
+    const int32_t* dist;
+    const int64_t* ids;
+    const int64_t* src;
+    const int64_t* id_map;
+    int64_t P, N;
+    int L, k;
+    CX_DEVICE int count(int64_t r) const {
+        int lo = 0, hi = k;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ids[r * k + mid] >= 0) lo = mid + 1; else hi = mid;
+        }
+        return lo;
+    }
+    CX_DEVICE int64_t id(int64_t r, int j) const {
+        const int64_t n = ids[r * k + j];
+        return id_map ? id_map[min(max(n, (int64_t)0), N - 1)] : n;
+    }
+    // entries of the sorted list r (n of them) that come before (dist, id).  Distances tie across lists all the time, so the
+    // comparison reads the REPORTED id wherever they do
+    CX_DEVICE int count_before(int64_t r, int n, int32_t dist_e, int64_t id_e) const {
+        int lo = 0, hi = n;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int32_t dm = dist[r * k + mid];
+            const bool b = dm != dist_e ? dm < dist_e : id(r, mid) < id_e;
+            if (b) lo = mid + 1; else hi = mid;
+        }
+        return lo;
+    }
+};
+
+// one wave per output row: merge the row's L sorted, disjoint lists into its top-k by (distance ascending, reported id
+// ascending).  Every list must be sorted in that order (a list whose reported ids ascend with its positions is: a k-means
+// list of an index sorted by a stable sort).  merge_lists_kernel<PaddedLists>'s job (search.hip) on integer distances.
+__global__ __launch_bounds__(256) void hamming_merge_lists_kernel(HammingLists S, int M, int32_t* __restrict__ out_d,
+                                                                  int64_t* __restrict__ out_id) {
+    __shared__ int64_t lrow_[4][MAXLISTS];
+    __shared__ int lcnt_[4][MAXLISTS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= M) return;   // (no workgroup barrier below)
+    const int L = S.L, k = S.k;
+    int64_t* lrow = lrow_[wave];
+    int* cnt = lcnt_[wave];
+    for (int l = lane; l < L; l += 64) {
+        const int64_t r = S.src[(int64_t)row * L + l];
+        const bool named = r >= 0 && r < S.P;
+        lrow[l] = named ? r : 0;
+        cnt[l] = named ? S.count(r) : 0;
+    }
+    wave_sync();
+    int total = 0;
+    for (int s = 0; s < L; ++s) total += cnt[s];
+    for (int idx = lane; idx < L * k; idx += 64) {
+        const int s = idx / k, j = idx - s * k;
+        if (j >= cnt[s]) continue;
+        const int32_t de = S.dist[lrow[s] * k + j];
+        const int64_t ie = S.id(lrow[s], j);
+        int rank = j;
+        for (int s2 = 0; s2 < L && rank < k; ++s2)
+            if (s2 != s && cnt[s2] > 0) rank += S.count_before(lrow[s2], cnt[s2], de, ie);
+        if (rank < k) {
+            out_d[(int64_t)row * k + rank] = de;
+            out_id[(int64_t)row * k + rank] = ie;
+        }
+    }
+    for (int r = min(total, k) + lane; r < k; r += 64) {
+        out_d[(int64_t)row * k + r] = INT_MAX;
+        out_id[(int64_t)row * k + r] = -1;
+    }
+}
+
+// ---- the k-majority update of a binary k-means (faiss IndexBinaryIVF's quantiser lives in the code domain) -----------------
+// centroid bit (l, b) = [2 * ones(l, b) > size(l)] over the member codes of list l.  All integer: any summation order gives
+// the same bits, so integer atomics are used freely and nothing here is a float.
+//
+// The rows arrive in any label order.  Five small launches turn them into per-list runs and count bits:
+//   km_count     sizes[l] = members of list l (one integer atomic per row); a label outside [0, nlist) joins no list
+//   km_scan      one workgroup: list_ptr = prefix of sizes, piece_ptr = prefix of ceil(sizes / KM_PIECE)
+//   km_scatter   order[list_ptr[l] + slot] = row, slot from an integer atomic on cursor[l] (the order INSIDE a list is
+//                whatever the atomics give; the sums do not see it)
+//   km_accumulate  one workgroup per piece (<= KM_PIECE rows of ONE list): the rows' code bytes are gathered into LDS, packed
+//                row after row; a thread owns one bit position (7 - (t & 7)) of four consecutive code bytes and keeps their four
+//                counts as the bytes of ONE register: count4 += (word >> shift) & 0x01010101 -- one LDS read, one shift-and, one
+//                add per row for four bits; no byte can overflow, a thread sees at most KM_PIECE = 128 rows.  2 nb threads
+//                cover a row of nb bytes, so 128 / nb groups of threads take the piece's rows round-robin (d = 768: 192
+//                threads busy, d = 64: 16 groups).  The piece's totals go to the (nlist, d) int32 table by integer atomics.
+//   km_finish    one wave per (list, 64 bits): threshold, ballot, pack_sign_kernel's bit reversal; an empty list is skipped
+constexpr int KM_PIECE = 128;
+
+__global__ __launch_bounds__(256) void km_zero_kernel(int* __restrict__ a, long na, int* __restrict__ b, long nb_) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < na; i += stride) a[i] = 0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nb_; i += stride) b[i] = 0;
+}
+
+__global__ __launch_bounds__(256) void km_count_kernel(const int32_t* __restrict__ labels, long n, int nlist,
+                                                       int* __restrict__ sizes) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const int l = labels[i];
+        if (l >= 0 && l < nlist) atomicAdd(&sizes[l], 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void km_scan_kernel(const int* __restrict__ sizes, int nlist, int* __restrict__ list_ptr,
+                                                      int* __restrict__ piece_ptr) {
+    __shared__ int rows_[256], pieces_[256];
+    const int tid = threadIdx.x;
+    const int per = (nlist + 255) / 256;
+    const int l0 = min(nlist, tid * per), l1 = min(nlist, l0 + per);
+    int rows = 0, pieces = 0;
+    for (int l = l0; l < l1; ++l) {
+        rows += sizes[l];
+        pieces += (sizes[l] + KM_PIECE - 1) / KM_PIECE;
+    }
+    rows_[tid] = rows;
+    pieces_[tid] = pieces;
+    __syncthreads();
+    rows = 0;
+    pieces = 0;
+    for (int t = 0; t < tid; ++t) {
+        rows += rows_[t];
+        pieces += pieces_[t];
+    }
+    for (int l = l0; l < l1; ++l) {
+        list_ptr[l] = rows;
+        piece_ptr[l] = pieces;
+        rows += sizes[l];
+        pieces += (sizes[l] + KM_PIECE - 1) / KM_PIECE;
+    }
+    if (tid == 255) {
+        list_ptr[nlist] = rows;
+        piece_ptr[nlist] = pieces;
+    }
+}
+
+__global__ __launch_bounds__(256) void km_scatter_kernel(const int32_t* __restrict__ labels, long n, int nlist,
+                                                         const int* __restrict__ list_ptr, int* __restrict__ cursor,
+                                                         int* __restrict__ order) {
+    const long stride = (long)gridDim.x * 256;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+        const int l = labels[i];
+        if (l >= 0 && l < nlist) order[list_ptr[l] + atomicAdd(&cursor[l], 1)] = (int)i;
+    }
+}
+
+__global__ __launch_bounds__(256) void km_accumulate_kernel(const uint8_t* __restrict__ codes, long ldc, int d, int nlist,
+                                                            const int* __restrict__ list_ptr, const int* __restrict__ piece_ptr,
+                                                            const int* __restrict__ order, int* __restrict__ ones) {
+    __shared__ __attribute__((aligned(16))) uint8_t rows_[KM_PIECE * 128];
+    const int tid = threadIdx.x, piece = blockIdx.x;
+    if (piece >= piece_ptr[nlist]) return;   // (the grid is the host's upper bound; uniform, before any barrier)
+    int lo = 0, hi = nlist;                  // the list l with piece_ptr[l] <= piece < piece_ptr[l + 1]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (piece_ptr[mid] <= piece) lo = mid; else hi = mid;
+    }
+    const int l = lo;
+    const int r0 = list_ptr[l] + (piece - piece_ptr[l]) * KM_PIECE;
+    const int nr = min(KM_PIECE, list_ptr[l + 1] - r0);
+    const int nb = d / 8, cpr = nb / 8;      // bytes and 8-byte chunks per row
+    for (int c = tid; c < nr * cpr; c += 256) {
+        const int r = c / cpr, q = c - r * cpr;
+        const uint2 v = *reinterpret_cast<const uint2*>(codes + (int64_t)order[r0 + r] * ldc + 8 * q);
+        *reinterpret_cast<uint2*>(rows_ + 8 * c) = v;   // row r at r * nb: packed
+    }
+    __syncthreads();
+    const int tpr = 2 * nb;                  // threads that cover one row: 8 bit positions x nb / 4 words
+    const int groups = 256 / tpr, g = tid / tpr, tl = tid - g * tpr;
+    if (g >= groups) return;
+    const int word = tl >> 3, shift = 7 - (tl & 7);   // dimension 8 B + i is bit 7 - i of byte B
+    uint32_t count4 = 0;
+    for (int r = g; r < nr; r += groups)
+        count4 += (*reinterpret_cast<const uint32_t*>(rows_ + r * nb + 4 * word) >> shift) & 0x01010101u;
+    int* out = ones + (int64_t)l * d;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = (count4 >> (8 * j)) & 0xff;   // byte j of the word: code byte 4 word + j
+        if (c) atomicAdd(&out[(4 * word + j) * 8 + (tl & 7)], c);
+    }
+}
+
+__global__ __launch_bounds__(256) void km_finish_kernel(const int* __restrict__ ones, const int* __restrict__ sizes, int nlist,
+                                                        int d, uint8_t* __restrict__ centroids) {
+    const int lane = threadIdx.x & 63;
+    const int upr = d / 64;
+    const long units = (long)nlist * upr, nwaves = (long)gridDim.x * 4;
+    for (long u = (long)blockIdx.x * 4 + (threadIdx.x >> 6); u < units; u += nwaves) {
+        const long l = u / upr;
+        const int c = (int)(u - l * upr);
+        const int size = sizes[l];
+        if (size == 0) continue;   // an empty list keeps its centroid bytes (wave-uniform)
+        const unsigned long long mask = __ballot(2 * (long)ones[l * d + c * 64 + lane] > (long)size);
+        const unsigned long long rev = __brevll(mask);
+        if (lane < 8) centroids[l * (d / 8) + c * 8 + lane] = (uint8_t)(rev >> (8 * (7 - lane)));
     }
 }
 
@@ -489,6 +769,90 @@ int cx_search_hamming_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, 
     }
     hipLaunchKernelGGL(hamming_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, s, lists, counts, M, N > 0 ? ns : 0, k,
                        out_dist, out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_search_hamming_window_ws_bytes(int M, int k) {
+    if (M <= 0 || k <= 0) return 0;
+    return (long)M * ((long)k * (long)sizeof(HCand) + (long)sizeof(int)) + 16;
+}
+
+int cx_search_hamming_window_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, int d, long ldq, long ldd, int k,
+                                  const int64_t* min_id, const int64_t* end_id, const int64_t* excl_ptr,
+                                  const int64_t* excl_ids, const int32_t* max_dist, void* ws, int32_t* out_dist,
+                                  int64_t* out_ids, void* stream) {
+    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!Qc || !out_dist || !out_ids || (N > 0 && (!Dc || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
+    if (ldq < d / 8 || (ldq % 8) != 0 || (N > 0 && (ldd < d / 8 || (ldd % 8) != 0))) return CX_ERR_ALIGN;
+    if (((uintptr_t)Qc & 7) || ((uintptr_t)Dc & 7) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    HCand* lists = reinterpret_cast<HCand*>(ws);
+    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
+    if (N > 0) {
+        WinHammingParams p = {};
+        p.Q = Qc; p.D = Dc; p.ldq = ldq; p.ldd = ldd;
+        p.M = M; p.N = (int)N; p.d = d; p.k = k;
+        p.nsplit = 1;   // one workgroup walks a query tile's whole band
+        p.tiles_n = (int)((N + TN - 1) / TN);
+        p.tiles_per_split = p.tiles_n;
+        p.xptr = excl_ptr; p.xids = excl_ids; p.maxd = max_dist;
+        p.min_id = min_id; p.end_id = end_id;
+        p.lists = lists; p.counts = counts;
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(&hamming_window_kernel), (int)sizeof(WinHammingLds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(hamming_window_kernel, dim3((M + TM - 1) / TM), dim3(256), sizeof(WinHammingLds), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    // the row's one list, padded, in the output layout
+    hipLaunchKernelGGL(hamming_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, s, lists, counts, M, N > 0 ? 1 : 0, k, out_dist,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+int cx_hamming_merge_lists(const int32_t* dist, const int64_t* ids, long P, int k, const int64_t* src, int M, int L,
+                           const int64_t* id_map, long N, int32_t* out_dist, int64_t* out_ids, void* stream) {
+    if (M < 0 || P < 0 || k < 1 || k > MAXK || L < 1 || L > MAXLISTS || (id_map && N < 1)) return CX_ERR_SHAPE;
+    if (M == 0) return CX_OK;
+    if (!src || !out_dist || !out_ids || (P > 0 && (!dist || !ids))) return CX_ERR_ARG;
+    const HammingLists S = {dist, ids, src, id_map, (int64_t)P, (int64_t)N, L, k};
+    hipLaunchKernelGGL(hamming_merge_lists_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, S, M, out_dist,
+                       out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+long cx_binary_kmeans_update_ws_bytes(long n, int d, int nlist) {
+    if (n <= 0 || d <= 0 || nlist <= 0) return 0;
+    // ones (nlist, d), cursor (nlist), list_ptr (nlist + 1), piece_ptr (nlist + 1), order (n): int32 each
+    return 4 * ((long)nlist * d + 3L * nlist + 2 + n) + 16;
+}
+
+int cx_binary_kmeans_update(const uint8_t* codes, long n, int d, long ldc, const int32_t* labels, int nlist, void* ws,
+                            uint8_t* centroids_inout, int32_t* sizes_out, void* stream) {
+    if (n < 0 || n > 0x7fffffffL || nlist < 1 || d < 64 || d > 1024 || (d % 64) != 0) return CX_ERR_SHAPE;
+    if (n == 0) return CX_OK;
+    if (!codes || !labels || !ws || !centroids_inout || !sizes_out) return CX_ERR_ARG;
+    if (ldc < d / 8 || (ldc % 8) != 0) return CX_ERR_ALIGN;
+    if (((uintptr_t)codes & 7) || ((uintptr_t)labels & 3) || ((uintptr_t)ws & 15) || ((uintptr_t)sizes_out & 3)) return CX_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int* ones = reinterpret_cast<int*>(ws);
+    int* cursor = ones + (int64_t)nlist * d;
+    int* list_ptr = cursor + nlist;
+    int* piece_ptr = list_ptr + nlist + 1;
+    int* order = piece_ptr + nlist + 1;
+    const long nz = (long)nlist * d + nlist;   // ones and cursor are adjacent
+    const int grid_n = (int)min((n + 255) / 256, 1L << 16);
+    hipLaunchKernelGGL(km_zero_kernel, dim3((int)min((nz + 255) / 256, 1L << 16)), dim3(256), 0, s, ones, nz, sizes_out,
+                       (long)nlist);
+    hipLaunchKernelGGL(km_count_kernel, dim3(grid_n), dim3(256), 0, s, labels, n, nlist, sizes_out);
+    hipLaunchKernelGGL(km_scan_kernel, dim3(1), dim3(256), 0, s, sizes_out, nlist, list_ptr, piece_ptr);
+    hipLaunchKernelGGL(km_scatter_kernel, dim3(grid_n), dim3(256), 0, s, labels, n, nlist, list_ptr, cursor, order);
+    const long pieces = min((n + KM_PIECE - 1) / KM_PIECE + nlist, n);   // >= sum of ceil(size / KM_PIECE); each piece has a row
+    hipLaunchKernelGGL(km_accumulate_kernel, dim3((unsigned)pieces), dim3(256), 0, s, codes, ldc, d, nlist, list_ptr, piece_ptr,
+                       order, ones);
+    const long units = (long)nlist * (d / 64);
+    hipLaunchKernelGGL(km_finish_kernel, dim3((int)min((units + 3) / 4, 1L << 16)), dim3(256), 0, s, ones, sizes_out, nlist, d,
+                       centroids_inout);
     return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
 }
 

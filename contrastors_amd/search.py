@@ -29,6 +29,11 @@ index of the nearest of 256 trained centroids of a dsub-wide sub-vector (`pq_enc
 by the bf16 tile kernel with its document panel gathered from the codebook (cx_search_pq_topk, csrc/search.hip): bit for bit
 `FlatIPIndex.search` over the decoded rows; `search_pq_rescored` re-scores its candidates exactly.
 
+`IVFBinaryIndex` is `_IVFLists`' lists over BinaryFlatIndex's codes with the quantiser in the code domain (faiss
+`IndexBinaryIVF`): centroid codes, Hamming assignment and probing, k-majority training (cx_binary_kmeans_update), the windowed
+Hamming scan and merge (cx_search_hamming_window_topk / cx_hamming_merge_lists, csrc/search_binary.hip);
+`search_ivf_binary_rescored` is its two-stage form.
+
 `encode` is the embedding side: this project's BiEncoder under no_grad, length-sorted batches, results in input order.
 """
 from __future__ import annotations
@@ -1512,10 +1517,11 @@ def pq_encode(x, codebooks):
     return codes
 
 
-def pq_train_rows(n: int, sample: Optional[int], seed: int):
+def pq_train_rows(n: int, sample: Optional[int], seed: int, first: int = PQ_KSUB):
     """The rows PQFlatIndex.train fits on and starts from -> (sample rows (ns,) int64 ascending, or None = all n rows;
     initial rows (256,) int64, positions INSIDE the sample).  The sample is KMeans.fit(sample=)'s seeded choice; the initial
-    centroids of every sub-quantiser are the sub-vectors of the first 256 rows of a permutation seeded the same way."""
+    centroids of every sub-quantiser are the sub-vectors of the first 256 rows of a permutation seeded the same way.
+    first: how many initial rows (IVFBinaryIndex.train starts from nlist of them)."""
     rows = None
     ns = n
     if sample is not None and int(sample) < n:
@@ -1523,7 +1529,7 @@ def pq_train_rows(n: int, sample: Optional[int], seed: int):
         rows = torch.randperm(n, generator=g)[: int(sample)].sort().values
         ns = int(sample)
     g = torch.Generator().manual_seed(seed)
-    return rows, torch.randperm(ns, generator=g)[:PQ_KSUB]
+    return rows, torch.randperm(ns, generator=g)[:first]
 
 
 class PQFlatIndex:
@@ -1961,6 +1967,228 @@ def search_ivf_pq_rescored(index: IVFPQIndex, vectors, queries, k: int, nprobe: 
             raise ValueError(f"below has {n_below} entries for {M} queries")
     qd = _to_device_2d(queries, index.d, index.device)
     cand = _paged_candidates(lambda kp, ex: index.search(qd, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+
+
+def _is_codes(x) -> bool:
+    """uint8 input is taken as packed sign codes, everything else as float rows (BinaryFlatIndex.add's rule)."""
+    dt = x.dtype if hasattr(x, "dtype") else np.asarray(x).dtype
+    return dt == torch.uint8 if isinstance(dt, torch.dtype) else np.dtype(dt) == np.uint8
+
+
+class IVFBinaryIndex(_IVFLists):
+    """Inverted-file index over packed sign codes on one GPU (faiss IndexBinaryIVF; d counts BITS): BinaryFlatIndex's codes,
+    d / 8 bytes per row, in the lists of a coarse quantiser that lives in the code domain -- the centroids are codes, rows are
+    assigned and lists probed by Hamming distance, and training is k-majority (cx_binary_kmeans_update) -- so the index works
+    from the codes alone.  _IVFLists' bookkeeping as it is (rows sorted by list with a stable sort, the pair plan, the pair
+    exclusions); the scan is one cx_search_hamming_window_topk launch per query batch over the (query, probed list) pairs and
+    cx_hamming_merge_lists merges each query's lists by (distance, original id).  Everything is an integer: nprobe == nlist is
+    BinaryFlatIndex.search bit for bit; search_ivf_binary_rescored re-scores the candidates exactly.  tests/ivf_binary_ref.py
+    is the contract.
+
+    Not here: the curation tools' flags, a cursor in place of page exclusions, save / load (centroids go in and out as
+    arrays), more than one GPU."""
+
+    _ENTRY = "cx_search_hamming_window_topk"
+
+    @property
+    def centroids(self) -> torch.Tensor:
+        """(nlist, d / 8) uint8: the centroid codes."""
+        self._require_trained()
+        return self._centroids
+
+    def _check_rows(self, x) -> Tuple[int, bool]:
+        """-> (n, whether x holds codes); a wrong shape raises (host only)."""
+        codes = _is_codes(x)
+        width = self.d // 8 if codes else self.d
+        if len(np.shape(x)) != 2 or np.shape(x)[1] != width:
+            what = f"(n, {width}) uint8 codes" if codes else f"a (n, {width}) array"
+            raise ValueError(f"expected {what}, got shape {tuple(np.shape(x))}")
+        return int(np.shape(x)[0]), codes
+
+    def _code_chunks(self, x, n: int, codes: bool):
+        """The n rows of x (a tensor anywhere, an array or a memmap) as codes on the device, QUANTIZE_ROWS rows at a time."""
+        if not codes:
+            for _, _, part in _float_chunks(x, n, self.device):
+                yield pack_sign_bits(part)
+            return
+        for r0 in range(0, n, QUANTIZE_ROWS):
+            part = x[r0: r0 + QUANTIZE_ROWS]
+            if not isinstance(part, torch.Tensor):
+                part = torch.from_numpy(np.array(part, dtype=np.uint8))   # (a copy: a read-only memmap slice)
+            # (never a view of the caller's tensor: the index keeps the chunk)
+            moved = part.to(self.device)
+            yield moved.clone(memory_format=torch.contiguous_format) if moved is part else moved.contiguous()
+
+    def _set_centroids(self, c: torch.Tensor) -> None:
+        """c (nlist, d / 8) uint8 on the device becomes the quantiser: a BinaryFlatIndex over that very tensor."""
+        self._centroids = c
+        self._coarse = BinaryFlatIndex(self.d, device=self.device, workspace_bytes=self.workspace_bytes)
+        self._coarse._store, self._coarse.ntotal = c, self.nlist
+
+    def train(self, x=None, max_iter: int = 10, sample: Optional[int] = None, centroids=None) -> None:
+        """Fit the nlist centroid codes to x (float rows, binarised by sign, or uint8 codes; a tensor anywhere, an array or a
+        memmap; host sources are sampled on the host) with max_iter k-majority rounds -- assign every sampled code to its
+        nearest centroid (Hamming, ties to the lower list), then set centroid bit b to 1 exactly when more than half of the
+        members have it (cx_binary_kmeans_update; an empty list keeps its code) -- from the codes of the first nlist rows of a
+        seeded permutation of the sample: the same x and seed give the same bytes; no convergence test, no restarts.  sample:
+        as PQFlatIndex.train (default min(n, 65 536); explicit values from 256 to 262 144); at least nlist rows are needed.
+        Or take a given (nlist, d / 8) uint8 table as it is."""
+        if (x is None) == (centroids is None):
+            raise ValueError("train: give either the training rows or centroids=")
+        if self.ntotal:
+            raise RuntimeError("train: the index holds rows labelled by the current centroids; reset() first")
+        nb = self.d // 8
+        if centroids is not None:
+            if tuple(np.shape(centroids)) != (self.nlist, nb) or not _is_codes(centroids):
+                raise ValueError(f"expected ({self.nlist}, {nb}) uint8 centroids, got shape {tuple(np.shape(centroids))}")
+            c = centroids if isinstance(centroids, torch.Tensor) else torch.from_numpy(np.array(centroids, dtype=np.uint8))
+            self._set_centroids(c.to(self.device).clone().contiguous())
+            return
+        n, codes = self._check_rows(x)
+        max_iter = int(max_iter)
+        if max_iter < 0:
+            raise ValueError(f"max_iter must not be negative, got {max_iter}")
+        if sample is not None and not PQ_KSUB <= int(sample) <= PQ_MAX_SAMPLE:
+            raise ValueError(f"sample must be in [{PQ_KSUB}, {PQ_MAX_SAMPLE}], got {sample}")
+        ns = min(n, PQ_DEFAULT_SAMPLE if sample is None else int(sample))
+        if ns < self.nlist:
+            raise ValueError(f"train: {self.nlist} centroids need at least {self.nlist} rows, got {ns}")
+        rows, first = pq_train_rows(n, ns, self.seed, first=self.nlist)
+        if rows is None:
+            xs = x
+        elif isinstance(x, torch.Tensor):
+            xs = x[rows.to(x.device)]
+        else:
+            xs = np.asarray(x[rows.numpy()])
+        parts = list(self._code_chunks(xs, ns, codes))
+        xc = parts[0] if len(parts) == 1 else torch.cat(parts)
+        c = xc[first.to(self.device)].contiguous()
+        self._set_centroids(c)
+        h = _C.lib()
+        sizes = torch.empty(self.nlist, dtype=torch.int32, device=self.device)
+        ws = torch.empty(h.cx_binary_kmeans_update_ws_bytes(ns, self.d, self.nlist), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for _ in range(max_iter):
+                labels = self._label(xc)
+                _C.check(h.cx_binary_kmeans_update(xc.data_ptr(), ns, self.d, nb, labels.data_ptr(), self.nlist, ws.data_ptr(),
+                                                   c.data_ptr(), sizes.data_ptr(), _C.cur_stream()), "cx_binary_kmeans_update")
+
+    def _label(self, xc: torch.Tensor) -> torch.Tensor:
+        """xc (n, d / 8) codes on the device -> (n,) int32: every row's list, the centroid code at the smallest Hamming
+        distance, ties to the lower list: cx_search_hamming_topk with k = 1, the first probe of the same code."""
+        return self._coarse.search(xc, 1)[1].reshape(-1).to(torch.int32)
+
+    def add(self, x) -> None:
+        """Append rows: float vectors are binarised by sign (x > 0), uint8 (n, d / 8) arrays are taken as codes (a tensor
+        anywhere, an array or a memmap); row i of the n-th add gets id ntotal + i.  The rows go through the device
+        QUANTIZE_ROWS at a time; each chunk of codes is labelled with the coarse index, then pushed."""
+        self._require_trained()
+        n, codes = self._check_rows(x)
+        if self.ntotal + n > MAX_NTOTAL:
+            raise ValueError(f"IVFBinaryIndex holds at most {MAX_NTOTAL} vectors")
+        for part in self._code_chunks(x, n, codes):
+            self._push((part,), self._label(part))
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """The stored codes in list order, (ntotal, d / 8) uint8 (a view): row p is the row add() gave the id _order[p]."""
+        self._finalise()
+        if self._cols is None:
+            return torch.empty(0, self.d // 8, dtype=torch.uint8, device=self.device)
+        return self._cols[0]
+
+    def _pair_row_bytes(self) -> int:
+        return self.d // 8 + 4
+
+    def search(self, queries, k: int, nprobe: int, exclude=None, max_dist=None):
+        """-> (dist (M, k) int32, ids (M, k) int64), the conventions of BinaryFlatIndex.search (ascending distance, ties to the
+        lower id, (INT32_MAX, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows
+        of the nprobe lists whose centroid codes are nearest to each query, 1 <= nprobe <= min(nlist, 256).  queries: float
+        rows or uint8 codes, as for add.  ids, and the ids of exclude, are the ids add() gave; max_dist is inclusive.
+        nprobe == nlist is BinaryFlatIndex.search, bit for bit."""
+        as_numpy = not isinstance(queries, torch.Tensor)
+        k, nprobe = int(k), int(nprobe)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        if not 1 <= nprobe <= min(self.nlist, MAX_NPROBE):
+            raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(self.nlist, MAX_NPROBE)}], got {nprobe}")
+        self._require_trained()
+        M, codes = self._check_rows(queries)
+        row_ptr, xhost = _exclusion_csr_host(exclude, M)
+        md = None
+        if max_dist is not None:
+            md = torch.as_tensor(np.asarray(max_dist) if not isinstance(max_dist, torch.Tensor) else max_dist)
+            if md.numel() != M:
+                raise ValueError(f"max_dist has {md.numel()} entries for {M} queries")
+            md = md.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        dist = torch.full((M, k), 2 ** 31 - 1, dtype=torch.int32, device=self.device)
+        ids = torch.full((M, k), -1, dtype=torch.int64, device=self.device)
+        if M and self.ntotal:
+            self._finalise()
+            h = _C.lib()
+            nb = self.d // 8
+            parts = list(self._code_chunks(queries, M, codes))
+            qc = parts[0] if len(parts) == 1 else torch.cat(parts)
+            D = self._cols[0]
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                probes = self._coarse.search(qc, nprobe)[1]
+                dptr = xids = None
+                if row_ptr is not None and xhost.numel():
+                    dptr, xids = row_ptr.to(self.device), xhost.to(self.device)
+                mq = self.batch_queries(M, k, nprobe)
+                for b0 in range(0, M, mq):
+                    m = min(mq, M - b0)
+                    P = m * nprobe
+                    pair_q, mid, end, src = ivf_pair_plan(probes[b0: b0 + m], self._list_ptr)
+                    mg = None if md is None else md[b0: b0 + m][pair_q]
+                    pptr = pids = None
+                    if dptr is not None:
+                        e0, e1 = int(row_ptr[b0]), int(row_ptr[b0 + m])      # (host copies)
+                        if e1 > e0:
+                            pptr, pids = ivf_pair_exclusions(dptr[b0: b0 + m + 1] - e0, xids[e0: e1], pair_q, self._inv, nprobe)
+                    ws = torch.empty(h.cx_search_hamming_window_ws_bytes(P, k), dtype=torch.uint8, device=self.device)
+                    ls = torch.empty(P, k, dtype=torch.int32, device=self.device)
+                    li = torch.empty(P, k, dtype=torch.int64, device=self.device)
+                    qg = qc[b0: b0 + m][pair_q]
+                    _C.check(h.cx_search_hamming_window_topk(qg.data_ptr(), D.data_ptr(), P, self.ntotal, self.d, nb, nb, k,
+                                                             mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
+                                                             _C.ptr(mg), ws.data_ptr(), ls.data_ptr(), li.data_ptr(), stream),
+                             "cx_search_hamming_window_topk")
+                    _C.check(h.cx_hamming_merge_lists(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
+                                                      self._order.data_ptr(), self.ntotal, dist[b0].data_ptr(),
+                                                      ids[b0].data_ptr(), stream), "cx_hamming_merge_lists")
+        if as_numpy:
+            return dist.cpu().numpy(), ids.cpu().numpy()
+        return dist, ids
+
+
+def search_ivf_binary_rescored(index: IVFBinaryIndex, vectors, queries, k: int, nprobe: int, rescore_factor: int = 4,
+                               exclude=None, below=None):
+    """search_binary_rescored over an IVFBinaryIndex: the min(k * rescore_factor, 4096) nearest codes among the rows of the
+    nprobe lists nearest to each query, then the k best of those by exact inner product with `vectors` (the corpus the index
+    was made from, in add() order: device bf16 rows, a host array or a memmap; see rescore).  queries: float rows (codes are
+    refused: the exact stage needs the floats), binarised by sign for the coarse stage.  exclude applies to the coarse stage,
+    below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it over the rows of the probed lists when
+    the candidate lists cover them."""
+    k, nprobe = int(k), int(nprobe)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    if not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
+        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
+    index._require_trained()
+    if _is_codes(queries):
+        raise ValueError("search_ivf_binary_rescored takes float queries, not codes")
+    as_numpy = not isinstance(queries, torch.Tensor)
+    M = index._check_rows(queries)[0]
+    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
+    if below is not None:
+        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
+        if n_below != M:
+            raise ValueError(f"below has {n_below} entries for {M} queries")
+    qd = _to_device_2d(queries, index.d, index.device)
+    qc = pack_sign_bits(qd)
+    cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
     return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
 
 

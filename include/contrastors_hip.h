@@ -509,6 +509,37 @@ int cx_search_hamming_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, 
 int cx_rescore_topk(const uint16_t* Q, const uint16_t* D, const int64_t* cand, const int64_t* ids, int M, long R, int d,
                     long ldq, long ldd, int c, int k, const float* below, float* out_scores, int64_t* out_ids,
                     void* stream);
+/* ---- IVF over sign codes (faiss IndexBinaryIVF: the coarse quantiser lives in the code domain; csrc/search_binary.hip).
+ *          Additive: cx_abi_version stays 10.  tests/ivf_binary_ref.py is the contract; nothing here is a float. -------------
+ * cx_search_hamming_window_topk: cx_search_hamming_topk's operands, alignment rules, refusals, order (distance ascending, ties
+ * to the lower id) and (INT32_MAX, -1) padding with cx_search_window_topk's window: row m admits document n only if
+ * min_id[m] < n < end_id[m] (min_id clamped to [-1, N], end_id to [0, N]; NULL = -1 / N everywhere; a row with
+ * end_id <= min_id + 1 has an empty window and is all padding).  A query tile walks the corpus tiles [t0, t1) of its rows'
+ * non-empty windows in one workgroup (no nsplit).  excl_ids are positions n; max_dist is inclusive.  With both window pointers
+ * NULL the output is cx_search_hamming_topk's bit for bit.  M == 0 and N == 0 as there.  ws: 16-B aligned,
+ * cx_search_hamming_window_ws_bytes(M, k) bytes, need not be initialised.  No value of the window arrays, exclusions or
+ * max_dist causes an access outside the operands.
+ * cx_hamming_merge_lists: cx_topk_merge_lists on such lists: dist / ids:(P,k) = P sorted lists padded with (INT32_MAX, -1)
+ * (a list ends at its first negative id); output row m merges the lists src[m][0 .. L), 1 <= L <= 256, an entry outside
+ * [0, P) names no list; id_map (or NULL, N >= 1 otherwise): the reported id of position n is id_map[n] (n clamped to [0, N)
+ * for the read).  Rank: (distance ascending, REPORTED id ascending) -- distances tie across lists all the time; every list must
+ * be sorted in that order and the lists of a row must be disjoint.  Padded with (INT32_MAX, -1).
+ * cx_binary_kmeans_update (the second half of a k-majority step): codes:(n,d/8) uint8, byte leading dimension ldc % 8 == 0,
+ * 8-B aligned; labels:(n) int32; centroids_inout:(nlist,d/8) uint8 contiguous; sizes_out:(nlist) int32.  For list l and bit
+ * b: ones = member codes with bit b set, size = member count; the new centroid bit is 1 exactly when 2 * ones > size; a list
+ * with size == 0 keeps its bytes; a label outside [0, nlist) joins no list.  Integer sums (integer atomics): the result does
+ * not depend on any order.  n <= 2^31 - 1; n == 0 is CX_OK without a launch (nothing is written).  ws: 16-B aligned,
+ * cx_binary_kmeans_update_ws_bytes(n, d, nlist) bytes, need not be initialised. */
+long cx_search_hamming_window_ws_bytes(int M, int k);
+int cx_search_hamming_window_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, int d, long ldq, long ldd, int k,
+                                  const int64_t* min_id, const int64_t* end_id, const int64_t* excl_ptr,
+                                  const int64_t* excl_ids, const int32_t* max_dist, void* ws, int32_t* out_dist,
+                                  int64_t* out_ids, void* stream);
+int cx_hamming_merge_lists(const int32_t* dist, const int64_t* ids, long P, int k, const int64_t* src, int M, int L,
+                           const int64_t* id_map, long N, int32_t* out_dist, int64_t* out_ids, void* stream);
+long cx_binary_kmeans_update_ws_bytes(long n, int d, int nlist);
+int cx_binary_kmeans_update(const uint8_t* codes, long n, int d, long ldc, const int32_t* labels, int nlist, void* ws,
+                            uint8_t* centroids_inout, int32_t* sizes_out, void* stream);
 /* ---- int8 scalar-quantised index (sentence-transformers "int8", faiss SQ8 with one range per row; csrc/quantize_int8.hip,
  *          csrc/search.hip).  Additive: cx_abi_version stays 10. ------------------------------------------------------------
  * cx_quantize_rows_int8: X:(rows,d) with leading dimension ldx ELEMENTS, dtype 0 = fp32, 1 = bf16 (cx_pack_sign_bits'
