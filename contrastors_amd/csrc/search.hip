@@ -682,6 +682,86 @@ int auto_splits(int M, long N, int nsplit) {
     return (int)max(1L, min((long)nsplit, tiles_n));
 }
 
+// ---- the host side of the six top-k entry points --------------------------------------------------------------------------
+
+// What every top-k entry point is given besides its operands.
+struct TopkArgs {
+    int M;
+    long N;
+    int d;
+    long ldq;
+    int k;
+    bool window;                      // the windowed form: min_id / end_id apply and one workgroup walks a query tile's whole band
+    const int64_t *min_id, *end_id;
+    const int64_t *excl_ptr, *excl_ids;
+    const float* below;
+    int nsplit;                       // corpus ranges per launch, 0 = chosen (not windowed)
+    void* ws;
+    float* out_scores;
+    int64_t* out_ids;
+    void* stream;
+};
+
+// The refusals, in the order of the return codes: CX_ERR_SHAPE, then M == 0 (CX_OK: the entry point returns it), then
+// CX_ERR_ARG, then CX_ERR_ALIGN.  shape_ok / args_ok / align_ok: the entry point's own part of each class (what its operands
+// need); Q: its query operand.
+int topk_checks(const TopkArgs& a, const void* Q, bool shape_ok, bool args_ok, bool align_ok) {
+    if (a.M < 0 || a.N < 0 || a.k < 1 || a.k > MAXK || a.d < 64 || a.d > 1024 || (a.d % 64) != 0 || a.N > MAX_N || !shape_ok)
+        return CX_ERR_SHAPE;
+    if (a.M == 0) return CX_OK;
+    if (!Q || !a.out_scores || !a.out_ids || (a.N > 0 && !a.ws) || (a.excl_ptr && !a.excl_ids) || !args_ok) return CX_ERR_ARG;
+    if (a.ldq < a.d || ((uintptr_t)Q & 15) || ((uintptr_t)a.ws & 15) || !align_ok) return CX_ERR_ALIGN;
+    return CX_OK;
+}
+
+// The fields every tiles kernel reads (Int8Params and PqParams are SearchParams): the shape, the row filters, the walk --
+// auto_splits corpus ranges, or one piece per query tile in the windowed form (the band is short) -- and the carve-up of the
+// workspace: lists (M, nsplit, k), then counts (M, nsplit).  N == 0: nothing walks, counts stays null and every row is padding.
+void topk_plan(const TopkArgs& a, SearchParams& p) {
+    const int ns = (a.N > 0 && !a.window) ? auto_splits(a.M, a.N, a.nsplit) : 1;
+    p.ldq = a.ldq;
+    p.M = a.M; p.N = (int)a.N; p.d = a.d; p.k = a.k;
+    p.nsplit = ns;
+    p.tiles_n = (int)((a.N + TN - 1) / TN);
+    p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
+    p.xptr = a.excl_ptr; p.xids = a.excl_ids; p.below = a.below;
+    p.min_id = a.min_id; p.end_id = a.end_id;
+    p.lists = reinterpret_cast<Cand*>(a.ws);
+    p.counts = a.N > 0 ? reinterpret_cast<int*>(p.lists + (int64_t)a.M * ns * a.k) : nullptr;
+}
+
+// Stage 1 with its LDS opt-in (one CxLdsOptIn per kernel: the static belongs to the kernel's instantiation of this template),
+// then stage 2: each row's nsplit lists, padded, into the output layout.
+template <class Lds, auto Kernel, class Params, class... Extra>
+int topk_launch(const TopkArgs& a, const Params& p, Extra... extra) {
+    hipStream_t s = (hipStream_t)a.stream;
+    if (p.N > 0) {
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(Kernel), (int)sizeof(Lds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(Kernel, dim3((p.M + TM - 1) / TM * p.nsplit), dim3(256), sizeof(Lds), s, p, extra...);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    const SplitLists S = {p.lists, p.counts, p.nsplit, p.k};
+    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((p.M + 3) / 4), dim3(256), 0, s, S, p.M, p.N > 0 ? p.nsplit : 0, p.k,
+                       a.out_scores, a.out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
+// bf16 rows: the corpus operand's part of the checks
+bool rows_given(long N, const void* D) { return N == 0 || D; }
+bool rows_aligned(long N, int d, long ldq, long ldd, const void* D, int ld_unit) {
+    return (ldq % ld_unit) == 0 && (N == 0 || (ldd >= d && (ldd % ld_unit) == 0)) && ((uintptr_t)D & 15) == 0;
+}
+
+// PQ codes: dsub, the operands' part of the checks and of the params
+bool pq_dsub_ok(int dsub) { return dsub == 8 || dsub == 16 || dsub == 32 || dsub == 64; }
+void pq_operands(PqParams& p, const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int dsub, long ldc) {
+    p.Q = Q;
+    p.codes = codes; p.cb = codebook; p.ldc = ldc; p.m = p.d / dsub;
+    p.lsub = dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6;
+    p.flat = (ldc == p.m && ((uintptr_t)codes & 15) == 0) ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -695,35 +775,13 @@ long cx_search_ws_bytes(int M, long N, int k, int nsplit) {
 int cx_search_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
                    const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, int nsplit, void* ws,
                    float* out_scores, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Q || !out_scores || !out_ids || (N > 0 && (!D || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
-    if (ldq < d || (ldq % 8) != 0 || (N > 0 && (ldd < d || (ldd % 8) != 0))) return CX_ERR_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
-    Cand* lists = reinterpret_cast<Cand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
-    if (N > 0) {
-        SearchParams p = {};
-        p.Q = Q; p.D = D; p.ldq = ldq; p.ldd = ldd;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = ns;
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
-        p.lists = lists; p.counts = counts;
-        const int tiles_m = (M + TM - 1) / TM;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel<false>), (int)sizeof(SearchLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_tiles_kernel<false>, dim3(tiles_m * ns), dim3(256), sizeof(SearchLds), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    // N == 0: counts stays null and every row is padding
-    const SplitLists S = {lists, counts, ns, k};
-    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    const TopkArgs a = {M, N, d, ldq, k, false, nullptr, nullptr, excl_ptr, excl_ids, below, nsplit, ws, out_scores, out_ids, stream};
+    const int rc = topk_checks(a, Q, true, rows_given(N, D), rows_aligned(N, d, ldq, ldd, D, 8));
+    if (rc != CX_OK || M == 0) return rc;
+    SearchParams p = {};
+    topk_plan(a, p);
+    p.Q = Q; p.D = D; p.ldd = ldd;
+    return topk_launch<SearchLds, search_tiles_kernel<false>>(a, p);
 }
 
 long cx_search_int8_ws_bytes(int M, long N, int k, int nsplit) { return cx_search_ws_bytes(M, N, k, nsplit); }
@@ -731,36 +789,14 @@ long cx_search_int8_ws_bytes(int M, long N, int k, int nsplit) { return cx_searc
 int cx_search_int8_topk(const int8_t* Q, const int8_t* D, const float* q_scale, const float* d_scale, int M, long N, int d,
                         long ldq, long ldd, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
                         int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Q || !q_scale || !out_scores || !out_ids || (N > 0 && (!D || !d_scale || !ws)) || (excl_ptr && !excl_ids))
-        return CX_ERR_ARG;
-    if (ldq < d || (ldq % 16) != 0 || (N > 0 && (ldd < d || (ldd % 16) != 0))) return CX_ERR_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
-    Cand* lists = reinterpret_cast<Cand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
-    if (N > 0) {
-        Int8Params p = {};
-        p.Q8 = Q; p.D8 = D; p.q_scale = q_scale; p.d_scale = d_scale; p.ldq = ldq; p.ldd = ldd;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = ns;
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
-        p.lists = lists; p.counts = counts;
-        const int tiles_m = (M + TM - 1) / TM;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel<false>), (int)sizeof(Int8SearchLds<false>)))
-            return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_int8_tiles_kernel<false>, dim3(tiles_m * ns), dim3(256), sizeof(Int8SearchLds<false>), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    const SplitLists S = {lists, counts, ns, k};
-    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    const TopkArgs a = {M, N, d, ldq, k, false, nullptr, nullptr, excl_ptr, excl_ids, below, nsplit, ws, out_scores, out_ids, stream};
+    const int rc = topk_checks(a, Q, true, q_scale && rows_given(N, D) && rows_given(N, d_scale),
+                               rows_aligned(N, d, ldq, ldd, D, 16));
+    if (rc != CX_OK || M == 0) return rc;
+    Int8Params p = {};
+    topk_plan(a, p);
+    p.Q8 = Q; p.D8 = D; p.q_scale = q_scale; p.d_scale = d_scale; p.ldd = ldd;
+    return topk_launch<Int8SearchLds<false>, search_int8_tiles_kernel<false>>(a, p);
 }
 
 long cx_search_pq_ws_bytes(int M, long N, int k, int nsplit) { return cx_search_ws_bytes(M, N, k, nsplit); }
@@ -768,39 +804,15 @@ long cx_search_pq_ws_bytes(int M, long N, int k, int nsplit) { return cx_search_
 int cx_search_pq_topk(const uint16_t* Q, const uint8_t* codes, const uint16_t* codebook, int M, long N, int d, int dsub,
                       long ldq, long ldc, int k, const int64_t* excl_ptr, const int64_t* excl_ids, const float* below,
                       int nsplit, void* ws, float* out_scores, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (dsub != 8 && dsub != 16 && dsub != 32 && dsub != 64) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Q || !out_scores || !out_ids || (N > 0 && (!codes || !codebook || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
-    const int m = d / dsub;
-    if (ldq < d || (ldq % 8) != 0 || (N > 0 && ldc < m)) return CX_ERR_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)codebook & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
-    Cand* lists = reinterpret_cast<Cand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
-    if (N > 0) {
-        PqParams p = {};
-        p.Q = Q; p.ldq = ldq;
-        p.codes = codes; p.cb = codebook; p.ldc = ldc; p.m = m;
-        p.lsub = dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6;
-        p.flat = (ldc == m && ((uintptr_t)codes & 15) == 0) ? 1 : 0;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = ns;
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
-        p.lists = lists; p.counts = counts;
-        const int tiles_m = (M + TM - 1) / TM;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_pq_tiles_kernel), (int)sizeof(PqSearchLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_pq_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(PqSearchLds), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    const SplitLists S = {lists, counts, ns, k};
-    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? ns : 0, k, out_scores,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    const TopkArgs a = {M, N, d, ldq, k, false, nullptr, nullptr, excl_ptr, excl_ids, below, nsplit, ws, out_scores, out_ids, stream};
+    const bool dsub_ok = pq_dsub_ok(dsub);
+    const int rc = topk_checks(a, Q, dsub_ok, rows_given(N, codes) && rows_given(N, codebook),
+                               (ldq % 8) == 0 && (N == 0 || !dsub_ok || ldc >= d / dsub) && ((uintptr_t)codebook & 15) == 0);
+    if (rc != CX_OK || M == 0) return rc;
+    PqParams p = {};
+    topk_plan(a, p);
+    pq_operands(p, Q, codes, codebook, dsub, ldc);
+    return topk_launch<PqSearchLds, search_pq_tiles_kernel>(a, p);
 }
 
 long cx_search_window_ws_bytes(int M, int k) {
@@ -811,34 +823,13 @@ long cx_search_window_ws_bytes(int M, int k) {
 int cx_search_window_topk(const uint16_t* Q, const uint16_t* D, int M, long N, int d, long ldq, long ldd, int k,
                           const int64_t* min_id, const int64_t* end_id, const int64_t* excl_ptr, const int64_t* excl_ids,
                           const float* below, void* ws, float* out_scores, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Q || !out_scores || !out_ids || (N > 0 && (!D || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
-    if (ldq < d || (ldq % 8) != 0 || (N > 0 && (ldd < d || (ldd % 8) != 0))) return CX_ERR_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    Cand* lists = reinterpret_cast<Cand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
-    if (N > 0) {
-        SearchParams p = {};
-        p.Q = Q; p.D = D; p.ldq = ldq; p.ldd = ldd;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = 1;   // one workgroup walks a query tile's whole band
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = p.tiles_n;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
-        p.min_id = min_id; p.end_id = end_id;
-        p.lists = lists; p.counts = counts;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_tiles_kernel<true>), (int)sizeof(WinSearchLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_tiles_kernel<true>, dim3((M + TM - 1) / TM), dim3(256), sizeof(WinSearchLds), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    // the row's one list, padded, in the output layout
-    const SplitLists S = {lists, counts, 1, k};
-    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? 1 : 0, k, out_scores,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    const TopkArgs a = {M, N, d, ldq, k, true, min_id, end_id, excl_ptr, excl_ids, below, 1, ws, out_scores, out_ids, stream};
+    const int rc = topk_checks(a, Q, true, rows_given(N, D), rows_aligned(N, d, ldq, ldd, D, 8));
+    if (rc != CX_OK || M == 0) return rc;
+    SearchParams p = {};
+    topk_plan(a, p);
+    p.Q = Q; p.D = D; p.ldd = ldd;
+    return topk_launch<WinSearchLds, search_tiles_kernel<true>>(a, p);
 }
 
 long cx_search_int8_window_ws_bytes(int M, int k) { return cx_search_window_ws_bytes(M, k); }
@@ -847,36 +838,14 @@ int cx_search_int8_window_topk(const int8_t* Q, const int8_t* D, const float* q_
                                int d, long ldq, long ldd, int k, const int64_t* min_id, const int64_t* end_id,
                                const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
                                float* out_scores, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Q || !q_scale || !out_scores || !out_ids || (N > 0 && (!D || !d_scale || !ws)) || (excl_ptr && !excl_ids))
-        return CX_ERR_ARG;
-    if (ldq < d || (ldq % 16) != 0 || (N > 0 && (ldd < d || (ldd % 16) != 0))) return CX_ERR_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)D & 15) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    Cand* lists = reinterpret_cast<Cand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
-    if (N > 0) {
-        Int8Params p = {};
-        p.Q8 = Q; p.D8 = D; p.q_scale = q_scale; p.d_scale = d_scale; p.ldq = ldq; p.ldd = ldd;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = 1;   // one workgroup walks a query tile's whole band
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = p.tiles_n;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
-        p.min_id = min_id; p.end_id = end_id;
-        p.lists = lists; p.counts = counts;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&search_int8_tiles_kernel<true>), (int)sizeof(Int8SearchLds<true>)))
-            return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(search_int8_tiles_kernel<true>, dim3((M + TM - 1) / TM), dim3(256), sizeof(Int8SearchLds<true>), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    // the row's one list, padded, in the output layout
-    const SplitLists S = {lists, counts, 1, k};
-    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? 1 : 0, k, out_scores,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    const TopkArgs a = {M, N, d, ldq, k, true, min_id, end_id, excl_ptr, excl_ids, below, 1, ws, out_scores, out_ids, stream};
+    const int rc = topk_checks(a, Q, true, q_scale && rows_given(N, D) && rows_given(N, d_scale),
+                               rows_aligned(N, d, ldq, ldd, D, 16));
+    if (rc != CX_OK || M == 0) return rc;
+    Int8Params p = {};
+    topk_plan(a, p);
+    p.Q8 = Q; p.D8 = D; p.q_scale = q_scale; p.d_scale = d_scale; p.ldd = ldd;
+    return topk_launch<Int8SearchLds<true>, search_int8_tiles_kernel<true>>(a, p);
 }
 
 long cx_search_pq_window_ws_bytes(int M, int k) { return cx_search_window_ws_bytes(M, k); }
@@ -885,48 +854,17 @@ int cx_search_pq_window_topk(const uint16_t* Q, const uint8_t* codes, const uint
                              long ldq, long ldc, int k, const int64_t* min_id, const int64_t* end_id, const float* bias,
                              const int64_t* excl_ptr, const int64_t* excl_ids, const float* below, void* ws,
                              float* out_scores, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (dsub != 8 && dsub != 16 && dsub != 32 && dsub != 64) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Q || !out_scores || !out_ids || (N > 0 && (!codes || !codebook || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
-    const int m = d / dsub;
-    if (ldq < d || (ldq % 8) != 0 || (N > 0 && ldc < m)) return CX_ERR_ALIGN;
-    if (((uintptr_t)Q & 15) || ((uintptr_t)codebook & 15) || ((uintptr_t)ws & 15) || ((uintptr_t)bias & 3)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    Cand* lists = reinterpret_cast<Cand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
-    if (N > 0) {
-        PqParams p = {};
-        p.Q = Q; p.ldq = ldq;
-        p.codes = codes; p.cb = codebook; p.ldc = ldc; p.m = m;
-        p.lsub = dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6;
-        p.flat = (ldc == m && ((uintptr_t)codes & 15) == 0) ? 1 : 0;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = 1;   // one workgroup walks a query tile's whole band
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = p.tiles_n;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.below = below;
-        p.min_id = min_id; p.end_id = end_id;
-        p.lists = lists; p.counts = counts;
-        const dim3 grid((M + TM - 1) / TM);
-        if (bias) {
-            static CxLdsOptIn opt;
-            if (!opt.ensure(reinterpret_cast<const void*>(&search_pq_window_kernel<true>), (int)sizeof(PqBiasSearchLds)))
-                return CX_ERR_LAUNCH;
-            hipLaunchKernelGGL(search_pq_window_kernel<true>, grid, dim3(256), sizeof(PqBiasSearchLds), s, p, bias);
-        } else {
-            static CxLdsOptIn opt;
-            if (!opt.ensure(reinterpret_cast<const void*>(&search_pq_window_kernel<false>), (int)sizeof(PqSearchLdsT<true>)))
-                return CX_ERR_LAUNCH;
-            hipLaunchKernelGGL(search_pq_window_kernel<false>, grid, dim3(256), sizeof(PqSearchLdsT<true>), s, p, bias);
-        }
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    // the row's one list, padded, in the output layout
-    const SplitLists S = {lists, counts, 1, k};
-    hipLaunchKernelGGL(merge_lists_kernel<SplitLists>, dim3((M + 3) / 4), dim3(256), 0, s, S, M, N > 0 ? 1 : 0, k, out_scores,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    const TopkArgs a = {M, N, d, ldq, k, true, min_id, end_id, excl_ptr, excl_ids, below, 1, ws, out_scores, out_ids, stream};
+    const bool dsub_ok = pq_dsub_ok(dsub);
+    const int rc = topk_checks(a, Q, dsub_ok, rows_given(N, codes) && rows_given(N, codebook),
+                               (ldq % 8) == 0 && (N == 0 || !dsub_ok || ldc >= d / dsub) && ((uintptr_t)codebook & 15) == 0 &&
+                                   ((uintptr_t)bias & 3) == 0);
+    if (rc != CX_OK || M == 0) return rc;
+    PqParams p = {};
+    topk_plan(a, p);
+    pq_operands(p, Q, codes, codebook, dsub, ldc);
+    if (bias) return topk_launch<PqBiasSearchLds, search_pq_window_kernel<true>>(a, p, bias);
+    return topk_launch<PqSearchLdsT<true>, search_pq_window_kernel<false>>(a, p, bias);
 }
 
 int cx_topk_merge_lists(const float* scores, const int64_t* ids, long P, int k, const int64_t* src, int M, int L,

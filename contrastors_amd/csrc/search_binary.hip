@@ -713,6 +713,44 @@ __global__ __launch_bounds__(256) void rescore_kernel(const bf16_t* __restrict__
     }
 }
 
+// ---- the host side of the two Hamming top-k entry points: p arrives with the operands and the row filters filled in ----------
+
+// The refusals, in the order of the return codes -- CX_ERR_SHAPE, then M == 0 (CX_OK: the entry point returns it), then
+// CX_ERR_ARG, then CX_ERR_ALIGN -- and then the plan: a walk in nsplit corpus ranges per query tile (0 = chosen; the windowed
+// form passes 1) and the carve-up of the workspace, lists (M, nsplit, k), then counts (M, nsplit).  N == 0: nothing walks,
+// counts stays null and every row is padding.
+int hamming_plan(HammingParams& p, long N, int nsplit, void* ws, const void* out_dist, const void* out_ids) {
+    if (p.M < 0 || N < 0 || p.k < 1 || p.k > MAXK || p.d < 64 || p.d > 1024 || (p.d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
+    if (p.M == 0) return CX_OK;
+    if (!p.Q || !out_dist || !out_ids || (N > 0 && (!p.D || !ws)) || (p.xptr && !p.xids)) return CX_ERR_ARG;
+    if (p.ldq < p.d / 8 || (p.ldq % 8) != 0 || (N > 0 && (p.ldd < p.d / 8 || (p.ldd % 8) != 0))) return CX_ERR_ALIGN;
+    if (((uintptr_t)p.Q & 7) || ((uintptr_t)p.D & 7) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
+    const int ns = N > 0 ? auto_splits(p.M, N, nsplit) : 1;
+    p.N = (int)N;
+    p.nsplit = ns;
+    p.tiles_n = (int)((N + TN - 1) / TN);
+    p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
+    p.lists = reinterpret_cast<HCand*>(ws);
+    p.counts = N > 0 ? reinterpret_cast<int*>(p.lists + (int64_t)p.M * ns * p.k) : nullptr;
+    return CX_OK;
+}
+
+// The tiles kernel with its LDS opt-in (one CxLdsOptIn per kernel: the static belongs to the kernel's instantiation of this
+// template), then the merge of each row's nsplit lists, padded, into the output layout.
+template <class Lds, auto Kernel, class Params>
+int hamming_launch(const Params& p, int32_t* out_dist, int64_t* out_ids, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (p.N > 0) {
+        static CxLdsOptIn opt;
+        if (!opt.ensure(reinterpret_cast<const void*>(Kernel), (int)sizeof(Lds))) return CX_ERR_LAUNCH;
+        hipLaunchKernelGGL(Kernel, dim3((p.M + TM - 1) / TM * p.nsplit), dim3(256), sizeof(Lds), s, p);
+        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(hamming_merge_kernel, dim3((p.M + 3) / 4), dim3(256), 0, s, p.lists, p.counts, p.M,
+                       p.N > 0 ? p.nsplit : 0, p.k, out_dist, out_ids);
+    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" {
@@ -743,33 +781,13 @@ long cx_search_hamming_ws_bytes(int M, long N, int k, int nsplit) {
 int cx_search_hamming_topk(const uint8_t* Qc, const uint8_t* Dc, int M, long N, int d, long ldq, long ldd, int k,
                            const int64_t* excl_ptr, const int64_t* excl_ids, const int32_t* max_dist, int nsplit, void* ws,
                            int32_t* out_dist, int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Qc || !out_dist || !out_ids || (N > 0 && (!Dc || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
-    if (ldq < d / 8 || (ldq % 8) != 0 || (N > 0 && (ldd < d / 8 || (ldd % 8) != 0))) return CX_ERR_ALIGN;
-    if (((uintptr_t)Qc & 7) || ((uintptr_t)Dc & 7) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const int ns = N > 0 ? auto_splits(M, N, nsplit) : 1;
-    HCand* lists = reinterpret_cast<HCand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * ns * k) : nullptr;
-    if (N > 0) {
-        HammingParams p = {};
-        p.Q = Qc; p.D = Dc; p.ldq = ldq; p.ldd = ldd;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = ns;
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = (p.tiles_n + ns - 1) / ns;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.maxd = max_dist;
-        p.lists = lists; p.counts = counts;
-        const int tiles_m = (M + TM - 1) / TM;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&hamming_tiles_kernel), (int)sizeof(HammingLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(hamming_tiles_kernel, dim3(tiles_m * ns), dim3(256), sizeof(HammingLds), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL(hamming_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, s, lists, counts, M, N > 0 ? ns : 0, k,
-                       out_dist, out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    HammingParams p = {};
+    p.Q = Qc; p.D = Dc; p.ldq = ldq; p.ldd = ldd;
+    p.M = M; p.d = d; p.k = k;
+    p.xptr = excl_ptr; p.xids = excl_ids; p.maxd = max_dist;
+    const int rc = hamming_plan(p, N, nsplit, ws, out_dist, out_ids);
+    if (rc != CX_OK || M == 0) return rc;
+    return hamming_launch<HammingLds, hamming_tiles_kernel>(p, out_dist, out_ids, stream);
 }
 
 long cx_search_hamming_window_ws_bytes(int M, int k) {
@@ -781,33 +799,14 @@ int cx_search_hamming_window_topk(const uint8_t* Qc, const uint8_t* Dc, int M, l
                                   const int64_t* min_id, const int64_t* end_id, const int64_t* excl_ptr,
                                   const int64_t* excl_ids, const int32_t* max_dist, void* ws, int32_t* out_dist,
                                   int64_t* out_ids, void* stream) {
-    if (M < 0 || N < 0 || k < 1 || k > MAXK || d < 64 || d > 1024 || (d % 64) != 0 || N > MAX_N) return CX_ERR_SHAPE;
-    if (M == 0) return CX_OK;
-    if (!Qc || !out_dist || !out_ids || (N > 0 && (!Dc || !ws)) || (excl_ptr && !excl_ids)) return CX_ERR_ARG;
-    if (ldq < d / 8 || (ldq % 8) != 0 || (N > 0 && (ldd < d / 8 || (ldd % 8) != 0))) return CX_ERR_ALIGN;
-    if (((uintptr_t)Qc & 7) || ((uintptr_t)Dc & 7) || ((uintptr_t)ws & 15)) return CX_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    HCand* lists = reinterpret_cast<HCand*>(ws);
-    int* counts = N > 0 ? reinterpret_cast<int*>(lists + (int64_t)M * k) : nullptr;
-    if (N > 0) {
-        WinHammingParams p = {};
-        p.Q = Qc; p.D = Dc; p.ldq = ldq; p.ldd = ldd;
-        p.M = M; p.N = (int)N; p.d = d; p.k = k;
-        p.nsplit = 1;   // one workgroup walks a query tile's whole band
-        p.tiles_n = (int)((N + TN - 1) / TN);
-        p.tiles_per_split = p.tiles_n;
-        p.xptr = excl_ptr; p.xids = excl_ids; p.maxd = max_dist;
-        p.min_id = min_id; p.end_id = end_id;
-        p.lists = lists; p.counts = counts;
-        static CxLdsOptIn opt;
-        if (!opt.ensure(reinterpret_cast<const void*>(&hamming_window_kernel), (int)sizeof(WinHammingLds))) return CX_ERR_LAUNCH;
-        hipLaunchKernelGGL(hamming_window_kernel, dim3((M + TM - 1) / TM), dim3(256), sizeof(WinHammingLds), s, p);
-        if (hipGetLastError() != hipSuccess) return CX_ERR_LAUNCH;
-    }
-    // the row's one list, padded, in the output layout
-    hipLaunchKernelGGL(hamming_merge_kernel, dim3((M + 3) / 4), dim3(256), 0, s, lists, counts, M, N > 0 ? 1 : 0, k, out_dist,
-                       out_ids);
-    return hipGetLastError() == hipSuccess ? CX_OK : CX_ERR_LAUNCH;
+    WinHammingParams p = {};
+    p.Q = Qc; p.D = Dc; p.ldq = ldq; p.ldd = ldd;
+    p.M = M; p.d = d; p.k = k;
+    p.xptr = excl_ptr; p.xids = excl_ids; p.maxd = max_dist;
+    p.min_id = min_id; p.end_id = end_id;
+    const int rc = hamming_plan(p, N, 1, ws, out_dist, out_ids);   // one workgroup walks a query tile's whole band
+    if (rc != CX_OK || M == 0) return rc;
+    return hamming_launch<WinHammingLds, hamming_window_kernel>(p, out_dist, out_ids, stream);
 }
 
 int cx_hamming_merge_lists(const int32_t* dist, const int64_t* ids, long P, int k, const int64_t* src, int M, int L,

@@ -34,6 +34,9 @@ by the bf16 tile kernel with its document panel gathered from the codebook (cx_s
 Hamming scan and merge (cx_search_hamming_window_topk / cx_hamming_merge_lists, csrc/search_binary.hip);
 `search_ivf_binary_rescored` is its two-stage form.
 
+The four flat indexes share `_FlatIndex` (the store, `batch_rows`, the batched launch of `search`), the four IVF indexes
+`_IVFLists` (the lists and the whole of `search`), the six `search_*_rescored` functions `_search_rescored`.
+
 `encode` is the embedding side: this project's BiEncoder under no_grad, length-sorted batches, results in input order.
 """
 from __future__ import annotations
@@ -77,16 +80,6 @@ def _exclusion_csr_host(exclude, M: int) -> Tuple[Optional[torch.Tensor], Option
     return row_ptr, ids
 
 
-def _exclusion_csr(exclude, M: int, device) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """exclude: None, a length-M sequence of id lists, or a (row_ptr (M+1), ids) pair -> int64 device CSR."""
-    row_ptr, ids = _exclusion_csr_host(exclude, M)
-    if row_ptr is None:
-        return None, None
-    if ids.numel() == 0:
-        ids = torch.zeros(1, dtype=torch.int64)   # a valid pointer; no row reads it
-    return row_ptr.to(device), ids.to(device)
-
-
 TILE = 128                         # rows per query tile and ids per corpus tile of the search kernels
 
 
@@ -118,41 +111,140 @@ def _window_ws_bytes(M: int, N: int, band_ptr: np.ndarray, mb: int, nsplit: int)
     return out
 
 
-class FlatIPIndex:
+def _row_bound(bound, M: int, name: str) -> Optional[torch.Tensor]:
+    """A per-row bound (`below`, `max_dist`: None, a tensor anywhere or an array) -> a tensor where it is; not M entries raises."""
+    if bound is None:
+        return None
+    bound = torch.as_tensor(np.asarray(bound) if not isinstance(bound, torch.Tensor) else bound)
+    if bound.numel() != M:
+        raise ValueError(f"{name} has {bound.numel()} entries for {M} queries")
+    return bound
+
+
+class _FlatIndex:
+    """What the flat indexes share: the growing store, the query batch and the batched launch of a search.  A subclass names its
+    top-k entry point and that entry's workspace-size function (_ENTRY, _WS_BYTES), the per-row bound and the dtype of the
+    returned scores (_BOUND, _OUT), says what is stored per row (_columns) and how queries are counted on the host
+    (_check_queries); its search() prepares the queries and makes the one kernel call (_search_batched)."""
+
+    _ENTRY = _WS_BYTES = ""
+    _BOUND = ("below", torch.float32)    # the per-row bound of search(): its keyword and the dtype the kernel reads
+    _OUT = torch.float32                 # scores (FlatIPIndex and the float codes) or int32 distances
+
+    def __init__(self, d: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
+        self.d = int(d)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU ({self._ENTRY}); there is no CPU path")
+        self.workspace_bytes = int(workspace_bytes)
+        self.reset()
+
+    def _columns(self) -> tuple:
+        """What is stored per row: (attribute, trailing shape, dtype) per column; rows [0, ntotal) of each are the corpus and
+        the first one is _store."""
+        raise NotImplementedError
+
+    def reset(self) -> None:
+        """Drop the stored rows (what was trained stays)."""
+        for attr, _, _ in self._columns():
+            setattr(self, attr, None)
+        self.ntotal = 0
+
+    def _view(self, attr: str) -> torch.Tensor:
+        """The first ntotal rows of a stored column (a view)."""
+        col = getattr(self, attr)
+        if col is None:
+            _, tail, dtype = next(c for c in self._columns() if c[0] == attr)
+            return torch.empty(0, *tail, dtype=dtype, device=self.device)
+        return col[: self.ntotal]
+
+    def reserve(self, n: int) -> None:
+        """Allocate room for n rows in total, so that adding a corpus in chunks never copies it."""
+        if n > MAX_NTOTAL:
+            raise ValueError(f"{type(self).__name__} holds at most {MAX_NTOTAL} vectors")
+        cap = 0 if self._store is None else self._store.shape[0]
+        if n > cap:
+            for attr, tail, dtype in self._columns():
+                grown = torch.empty(n, *tail, dtype=dtype, device=self.device)
+                if self.ntotal:
+                    grown[: self.ntotal].copy_(getattr(self, attr)[: self.ntotal])
+                setattr(self, attr, grown)
+
+    def batch_rows(self, M: int, k: int) -> int:
+        """The largest query batch (all of M, else halved down to a multiple of 128) whose workspace fits the bound."""
+        ws_bytes = getattr(_C.lib(), self._WS_BYTES)
+        m = M
+        while m > 128 and ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
+            m = max(128, (m // 2) // 128 * 128)
+        return m
+
+    def _check_queries(self, queries) -> int:
+        """-> M; a wrong shape raises (host only)."""
+        if len(np.shape(queries)) != 2 or np.shape(queries)[1] != self.d:
+            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(queries))}")
+        return int(np.shape(queries)[0])
+
+    def _search_batched(self, queries, k: int, exclude, bound, nsplit: int, as_numpy: bool, prepare):
+        """The search of every flat index.  On the host first: k, the query shape (_check_queries), the exclusion CSR and the
+        size of the per-row bound; then prepare() -- the class's last refusal (an untrained index), the queries onto the device
+        -- which returns launch(h, b0, m, tail): one call of the entry point for query rows [b0, b0 + m), where tail is the
+        entry points' common last arguments (excl_ptr, excl_ids, the bound, nsplit, ws, the two outputs and the stream, the
+        per-row ones offset to b0).  Batches of batch_rows() rows share one workspace.  -> (scores or distances (M, k), ids
+        (M, k) int64), as numpy arrays if as_numpy."""
+        k = int(k)
+        if not 1 <= k <= MAX_K:
+            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
+        M = self._check_queries(queries)
+        xptr, xids = _exclusion_csr_host(exclude, M)
+        bnd = _row_bound(bound, M, self._BOUND[0])
+        launch = prepare()
+        if bnd is not None:
+            bnd = bnd.to(device=self.device, dtype=self._BOUND[1]).reshape(-1).contiguous()
+        if xptr is not None:
+            xptr = xptr.to(self.device)
+            # (an empty id array still needs a valid pointer; no row reads it)
+            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
+        out = torch.empty(M, k, dtype=self._OUT, device=self.device)
+        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
+        if M:
+            h = _C.lib()
+            ws_bytes = getattr(h, self._WS_BYTES)
+            with torch.cuda.device(self.device):
+                stream = _C.cur_stream()
+                mb = self.batch_rows(M, k)
+                ws = None
+                if self.ntotal:
+                    # the split count (and so the scratch) follows the batch's rows: size it for both batch sizes used
+                    last = M - (M - 1) // mb * mb
+                    nbytes = max(ws_bytes(mb, self.ntotal, k, nsplit), ws_bytes(last, self.ntotal, k, nsplit))
+                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+                for b0 in range(0, M, mb):
+                    launch(h, b0, min(mb, M - b0),
+                           (None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
+                            None if bnd is None else bnd[b0:].data_ptr(), int(nsplit), _C.ptr(ws), out[b0].data_ptr(),
+                            ids[b0].data_ptr(), stream))
+        if as_numpy:
+            return out.cpu().numpy(), ids.cpu().numpy()
+        return out, ids
+
+
+class FlatIPIndex(_FlatIndex):
     """Exact maximum-inner-product index over bf16 vectors on one GPU (faiss IndexFlatIP with useFloat16)."""
+
+    _ENTRY, _WS_BYTES = "cx_search_topk", "cx_search_ws_bytes"
 
     def __init__(self, d: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
         if d % 64 or not 64 <= d <= 1024:
             raise ValueError(f"d must be a multiple of 64 in [64, 1024], got {d}")
-        self.d = int(d)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("FlatIPIndex runs on the GPU (cx_search_topk); there is no CPU path")
-        self.workspace_bytes = int(workspace_bytes)
-        self._store: Optional[torch.Tensor] = None   # (capacity, d) bf16; rows [0, ntotal) are the corpus
-        self.ntotal = 0
+        super().__init__(d, device, workspace_bytes)
 
-    def reset(self) -> None:
-        self._store = None
-        self.ntotal = 0
+    def _columns(self) -> tuple:
+        return (("_store", (self.d,), torch.bfloat16),)
 
     @property
     def vectors(self) -> torch.Tensor:
         """The stored corpus, (ntotal, d) bf16 (a view)."""
-        if self._store is None:
-            return torch.empty(0, self.d, dtype=torch.bfloat16, device=self.device)
-        return self._store[: self.ntotal]
-
-    def reserve(self, n: int) -> None:
-        """Allocate room for n vectors in total, so that adding a corpus in chunks never copies it."""
-        if n > MAX_NTOTAL:
-            raise ValueError(f"FlatIPIndex holds at most {MAX_NTOTAL} vectors")
-        cap = 0 if self._store is None else self._store.shape[0]
-        if n > cap:
-            grown = torch.empty(n, self.d, dtype=torch.bfloat16, device=self.device)
-            if self.ntotal:
-                grown[: self.ntotal].copy_(self._store[: self.ntotal])
-            self._store = grown
+        return self._view("_store")
 
     def add(self, x) -> None:
         """Append rows; fp32 / fp16 inputs are rounded to bf16 (round-to-nearest-even) as faiss rounds to fp16.
@@ -163,58 +255,18 @@ class FlatIPIndex:
         self._store[self.ntotal: self.ntotal + n].copy_(x)
         self.ntotal += n
 
-    def batch_rows(self, M: int, k: int) -> int:
-        """The largest query batch (all of M, else halved down to a multiple of 128) whose workspace fits the bound."""
-        h = _C.lib()
-        m = M
-        while m > 128 and h.cx_search_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
-            m = max(128, (m // 2) // 128 * 128)
-        return m
-
     def search(self, queries, k: int, exclude=None, below=None, nsplit: int = 0):
         """-> (scores (M, k) float32, ids (M, k) int64): per query the k largest inner products with the stored vectors,
         descending, ties to the lower id; missing entries are (-inf, -1).  exclude: per-row ids never returned (a list of
         id lists or a CSR (row_ptr, ids) pair); below: per-row exclusive upper bound on the score.  numpy in -> numpy
         out, torch in -> torch out on the index's device.  nsplit: corpus ranges per launch (0 = chosen; no effect on the
         result)."""
-        as_numpy = not isinstance(queries, torch.Tensor)
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-        q = _to_device_2d(queries, self.d, self.device)
-        M = q.shape[0]
-        xptr, xids = _exclusion_csr(exclude, M, self.device)
-        bel = None
-        if below is not None:
-            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
-            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-            if bel.numel() != M:
-                raise ValueError(f"below has {bel.numel()} entries for {M} queries")
-        scores = torch.empty(M, k, dtype=torch.float32, device=self.device)
-        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
-        if M:
-            h = _C.lib()
-            with torch.cuda.device(self.device):
-                stream = _C.cur_stream()
-                mb = self.batch_rows(M, k)
-                ws = None
-                if self.ntotal:
-                    # the split count (and so the scratch) follows the batch's rows: size it for both batch sizes used
-                    last = M - (M - 1) // mb * mb
-                    nbytes = max(h.cx_search_ws_bytes(mb, self.ntotal, k, nsplit),
-                                 h.cx_search_ws_bytes(last, self.ntotal, k, nsplit))
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                D = self.vectors
-                for b0 in range(0, M, mb):
-                    m = min(mb, M - b0)
-                    _C.check(h.cx_search_topk(q[b0].data_ptr(), D.data_ptr() if self.ntotal else None, m, self.ntotal,
-                                              self.d, self.d, self.d, k,
-                                              None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
-                                              None if bel is None else bel[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
-                                              scores[b0].data_ptr(), ids[b0].data_ptr(), stream), "cx_search_topk")
-        if as_numpy:
-            return scores.cpu().numpy(), ids.cpu().numpy()
-        return scores, ids
+        def prepare():
+            q = _to_device_2d(queries, self.d, self.device)
+            D = self.vectors.data_ptr() if self.ntotal else None
+            return lambda h, b0, m, tail: _C.check(
+                h.cx_search_topk(q[b0].data_ptr(), D, m, self.ntotal, self.d, self.d, self.d, int(k), *tail), "cx_search_topk")
+        return self._search_batched(queries, k, exclude, below, nsplit, not isinstance(queries, torch.Tensor), prepare)
 
     def rank_batch_rows(self, row_ptr: torch.Tensor, nsplit: int = 0) -> int:
         """The largest query batch (all rows, else halved down to a multiple of 128) whose cx_rank_ws_bytes -- for the batch
@@ -481,9 +533,13 @@ class _IVFLists:
     """The list bookkeeping of the inverted-file indexes: the coarse quantiser, labelling, the pending chunks, the stable sort
     by label, the pair plan of a search and the merge.  A subclass supplies what is stored per row (a tuple of tensors per chunk,
     kept in self._cols in list order), how many bytes a gathered pair row takes (_pair_row_bytes), how queries are taken
-    (_check_queries / _prepare_queries) and which kernel entry scans the pair rows (_ENTRY, _scan)."""
+    (_check_queries / _prepare_queries), which kernel entry scans the pair rows (_ENTRY, _scan) and, where the scan does not
+    write float scores, what its lists hold and which entries size and merge them (_WS_BYTES, _MERGE, _BOUND, _LIST)."""
 
     _ENTRY = ""                      # the windowed top-k entry point of the list scan
+    _WS_BYTES, _MERGE = "cx_search_window_ws_bytes", "cx_topk_merge_lists"   # its workspace size; the per-query merge
+    _BOUND = ("below", torch.float32)            # the per-row bound of search(): its name and the dtype the scan reads
+    _LIST = (torch.float32, -float("inf"))       # dtype of a list's scores and what a missing entry holds
 
     def __init__(self, d: int, nlist: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
         name = type(self).__name__
@@ -629,7 +685,7 @@ class _IVFLists:
         return int(np.shape(queries)[0])
 
     def _prepare_queries(self, queries):
-        """-> (the queries rounded to bf16 on the device, for the coarse probe; what _scan gathers its pair rows from)."""
+        """-> (the queries as the coarse index takes them, on the device; what _scan gathers its pair rows from)."""
         raise NotImplementedError
 
     def _pair_bias(self, coarse_scores: torch.Tensor, src: torch.Tensor) -> Optional[torch.Tensor]:
@@ -651,14 +707,11 @@ class _IVFLists:
         self._require_trained()
         M = self._check_queries(queries)
         row_ptr, xhost = _exclusion_csr_host(exclude, M)
-        bel = None
-        if below is not None:
-            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
-            if bel.numel() != M:
-                raise ValueError(f"below has {bel.numel()} entries for {M} queries")
-            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        bel = _row_bound(below, M, self._BOUND[0])
+        if bel is not None:
+            bel = bel.to(device=self.device, dtype=self._BOUND[1]).reshape(-1).contiguous()
         q, prepared = self._prepare_queries(queries)
-        scores = torch.full((M, k), -float("inf"), dtype=torch.float32, device=self.device)
+        scores = torch.full((M, k), self._LIST[1], dtype=self._LIST[0], device=self.device)
         ids = torch.full((M, k), -1, dtype=torch.int64, device=self.device)
         if M and self.ntotal:
             self._finalise()
@@ -680,14 +733,14 @@ class _IVFLists:
                         e0, e1 = int(row_ptr[b0]), int(row_ptr[b0 + m])      # (host copies)
                         if e1 > e0:
                             pptr, pids = ivf_pair_exclusions(dptr[b0: b0 + m + 1] - e0, xids[e0: e1], pair_q, self._inv, nprobe)
-                    ws = torch.empty(h.cx_search_window_ws_bytes(P, k), dtype=torch.uint8, device=self.device)
-                    ls = torch.empty(P, k, dtype=torch.float32, device=self.device)
+                    ws = torch.empty(getattr(h, self._WS_BYTES)(P, k), dtype=torch.uint8, device=self.device)
+                    ls = torch.empty(P, k, dtype=self._LIST[0], device=self.device)
                     li = torch.empty(P, k, dtype=torch.int64, device=self.device)
                     bias = self._pair_bias(coarse[b0: b0 + m], src)
                     self._scan(h, prepared, b0, m, pair_q, k, mid, end, pptr, pids, bg, bias, ws, ls, li, stream)
-                    _C.check(h.cx_topk_merge_lists(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
-                                                   self._order.data_ptr(), self.ntotal, scores[b0].data_ptr(),
-                                                   ids[b0].data_ptr(), stream), "cx_topk_merge_lists")
+                    _C.check(getattr(h, self._MERGE)(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
+                                                     self._order.data_ptr(), self.ntotal, scores[b0].data_ptr(),
+                                                     ids[b0].data_ptr(), stream), self._MERGE)
         if as_numpy:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
@@ -789,41 +842,28 @@ def pack_sign_bits(x):
     return out
 
 
-class BinaryFlatIndex:
+class BinaryFlatIndex(_FlatIndex):
     """Exact Hamming index over sign codes on one GPU (faiss IndexBinaryFlat; d counts BITS): d / 8 bytes per vector where
     FlatIPIndex keeps 2 d.  Same surface as FlatIPIndex; distances come from cx_search_hamming_topk (csrc/search_binary.hip)."""
 
+    _ENTRY, _WS_BYTES = "cx_search_hamming_topk", "cx_search_hamming_ws_bytes"
+    _BOUND = ("max_dist", torch.int32)
+    _OUT = torch.int32
+
     def __init__(self, d: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
         _check_code_dim(d)
-        self.d = int(d)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("BinaryFlatIndex runs on the GPU (cx_search_hamming_topk); there is no CPU path")
-        self.workspace_bytes = int(workspace_bytes)
-        self._store: Optional[torch.Tensor] = None   # (capacity, d / 8) uint8; rows [0, ntotal) are the corpus
-        self.ntotal = 0
+        super().__init__(d, device, workspace_bytes)
 
-    def reset(self) -> None:
-        self._store = None
-        self.ntotal = 0
+    def _columns(self) -> tuple:
+        return (("_store", (self.d // 8,), torch.uint8),)
 
     @property
     def codes(self) -> torch.Tensor:
         """The stored codes, (ntotal, d / 8) uint8 (a view)."""
-        if self._store is None:
-            return torch.empty(0, self.d // 8, dtype=torch.uint8, device=self.device)
-        return self._store[: self.ntotal]
+        return self._view("_store")
 
-    def reserve(self, n: int) -> None:
-        """Allocate room for n codes in total, so that adding a corpus in chunks never copies it."""
-        if n > MAX_NTOTAL:
-            raise ValueError(f"BinaryFlatIndex holds at most {MAX_NTOTAL} vectors")
-        cap = 0 if self._store is None else self._store.shape[0]
-        if n > cap:
-            grown = torch.empty(n, self.d // 8, dtype=torch.uint8, device=self.device)
-            if self.ntotal:
-                grown[: self.ntotal].copy_(self._store[: self.ntotal])
-            self._store = grown
+    def _check_queries(self, queries) -> int:
+        return int(np.shape(queries)[0])    # (_codes_of checks the shape on the host before it moves anything)
 
     def _codes_of(self, x) -> torch.Tensor:
         """(n, d) float rows (binarised by sign) or (n, d / 8) uint8 codes -> codes on the index's device."""
@@ -846,60 +886,19 @@ class BinaryFlatIndex:
         self._store[self.ntotal: self.ntotal + n].copy_(c)
         self.ntotal += n
 
-    def batch_rows(self, M: int, k: int) -> int:
-        h = _C.lib()
-        m = M
-        while m > 128 and h.cx_search_hamming_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
-            m = max(128, (m // 2) // 128 * 128)
-        return m
-
     def search(self, queries, k: int, exclude=None, max_dist=None, nsplit: int = 0):
         """-> (dist (M, k) int32, ids (M, k) int64): per query the k nearest stored codes by Hamming distance, ascending, ties
         to the lower id; missing entries are (INT32_MAX, -1).  queries: float rows or uint8 codes, as for add.  exclude: as
         FlatIPIndex.search; max_dist: per-row INCLUSIVE upper bound on the distance.  numpy in -> numpy out, torch in -> torch
         out on the index's device.  nsplit has no effect on the result."""
-        as_numpy = not isinstance(queries, torch.Tensor)
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-        M = int(np.shape(queries)[0])
-        xptr, xids = _exclusion_csr_host(exclude, M)
-        q = self._codes_of(queries)
-        if xptr is not None:
-            xptr = xptr.to(self.device)
-            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
-        md = None
-        if max_dist is not None:
-            md = torch.as_tensor(np.asarray(max_dist) if not isinstance(max_dist, torch.Tensor) else max_dist)
-            md = md.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-            if md.numel() != M:
-                raise ValueError(f"max_dist has {md.numel()} entries for {M} queries")
-        dist = torch.empty(M, k, dtype=torch.int32, device=self.device)
-        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
-        if M:
-            h = _C.lib()
+        def prepare():
+            q = self._codes_of(queries)
+            D = self.codes.data_ptr() if self.ntotal else None
             nb = self.d // 8
-            with torch.cuda.device(self.device):
-                stream = _C.cur_stream()
-                mb = self.batch_rows(M, k)
-                ws = None
-                if self.ntotal:
-                    last = M - (M - 1) // mb * mb
-                    nbytes = max(h.cx_search_hamming_ws_bytes(mb, self.ntotal, k, nsplit),
-                                 h.cx_search_hamming_ws_bytes(last, self.ntotal, k, nsplit))
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                D = self.codes
-                for b0 in range(0, M, mb):
-                    m = min(mb, M - b0)
-                    _C.check(h.cx_search_hamming_topk(q[b0].data_ptr(), D.data_ptr() if self.ntotal else None, m,
-                                                      self.ntotal, self.d, nb, nb, k,
-                                                      None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
-                                                      None if md is None else md[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
-                                                      dist[b0].data_ptr(), ids[b0].data_ptr(), stream),
-                             "cx_search_hamming_topk")
-        if as_numpy:
-            return dist.cpu().numpy(), ids.cpu().numpy()
-        return dist, ids
+            return lambda h, b0, m, tail: _C.check(
+                h.cx_search_hamming_topk(q[b0].data_ptr(), D, m, self.ntotal, self.d, nb, nb, int(k), *tail),
+                "cx_search_hamming_topk")
+        return self._search_batched(queries, k, exclude, max_dist, nsplit, not isinstance(queries, torch.Tensor), prepare)
 
 
 RESCORE_UPLOAD_BYTES = 1 << 30   # host sources: bf16 bytes of gathered rows uploaded per query batch, at most
@@ -1026,6 +1025,30 @@ def _check_rescored_arguments(index, vectors, k: int, rescore_factor: int) -> in
     return max(k, min(k * int(rescore_factor), MAX_CANDIDATES))
 
 
+def _search_rescored(index, vectors, queries, k: int, rescore_factor: int, exclude, below, coarse_queries, search_page,
+                     nprobe: Optional[int] = None):
+    """The two-stage search behind the search_*_rescored functions.  Host checks first, in one order for all of them: k,
+    rescore_factor and the row count of vectors; nprobe (the IVF indexes); the shape of the float queries; the exclusion CSR;
+    the size of below; trained (last, as in PQFlatIndex.search).  Then the float queries go to the device rounded to bf16 (qd,
+    the exact stage's), coarse_queries(queries, qd) makes what the index's search takes, search_page(qc, kp, exclude) -> its
+    (M, kp) ids serves _paged_candidates, and _rescore_candidates scores the candidates against vectors."""
+    k = int(k)
+    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
+    if nprobe is not None and not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
+        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
+    if len(np.shape(queries)) != 2 or np.shape(queries)[1] != index.d:
+        raise ValueError(f"expected a (n, {index.d}) array, got shape {tuple(np.shape(queries))}")
+    M = int(np.shape(queries)[0])
+    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
+    _row_bound(below, M, "below")
+    if hasattr(index, "_require_trained"):
+        index._require_trained()
+    qd = _to_device_2d(queries, index.d, index.device)
+    qc = coarse_queries(queries, qd)
+    cand = _paged_candidates(lambda kp, ex: search_page(qc, kp, ex), M, c, index.ntotal, exclude)
+    return _rescore_candidates(qd, cand, vectors, k, below, index.device, not isinstance(queries, torch.Tensor))
+
+
 def search_binary_rescored(index: BinaryFlatIndex, vectors, queries, k: int, rescore_factor: int = 4, exclude=None,
                            below=None):
     """Coarse Hamming search + exact re-scoring: the min(k * rescore_factor, 4096) nearest codes of `index` per query, then
@@ -1033,14 +1056,8 @@ def search_binary_rescored(index: BinaryFlatIndex, vectors, queries, k: int, res
     applies to the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it when the
     candidate lists cover the corpus.  Lists longer than the Hamming kernel's k bound (1024) are fetched in pages
     (_paged_candidates)."""
-    k = int(k)
-    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
-    as_numpy = not isinstance(queries, torch.Tensor)
-    M = int(np.shape(queries)[0])
-    qd = _to_device_2d(queries, index.d, index.device)
-    qc = pack_sign_bits(qd)
-    cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
-    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+    return _search_rescored(index, vectors, queries, k, rescore_factor, exclude, below, lambda q, qd: pack_sign_bits(qd),
+                            lambda qc, kp, ex: index.search(qc, kp, exclude=ex)[1])
 
 
 INT8_ZERO_AMAX = 2.0 ** -100     # rows whose largest magnitude is below this quantise to zero codes and a zero scale
@@ -1122,55 +1139,31 @@ def _is_code_pair(x) -> bool:
     return isinstance(x, tuple) and len(x) == 2
 
 
-class Int8FlatIndex:
+class Int8FlatIndex(_FlatIndex):
     """Maximum-inner-product index over int8 scalar-quantised rows on one GPU (faiss IndexScalarQuantizer QT_8bit with one
     range per row; sentence-transformers "int8"): d bytes + one fp32 scale per vector where FlatIPIndex keeps 2 d bytes.  Same
     surface as FlatIPIndex / BinaryFlatIndex.  The score of a pair is ((float)(q_codes . d_codes) * d_scale) * q_scale with an
     exact integer dot product (cx_search_int8_topk, csrc/search.hip): queries are quantised per row as the corpus is.
     search_int8_rescored re-scores its candidates exactly against the float rows."""
 
+    _ENTRY, _WS_BYTES = "cx_search_int8_topk", "cx_search_int8_ws_bytes"
+
     def __init__(self, d: int, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES):
         _check_code_dim(d)
-        self.d = int(d)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("Int8FlatIndex runs on the GPU (cx_search_int8_topk); there is no CPU path")
-        self.workspace_bytes = int(workspace_bytes)
-        self._store: Optional[torch.Tensor] = None    # (capacity, d) int8; rows [0, ntotal) are the corpus
-        self._scale: Optional[torch.Tensor] = None    # (capacity,) fp32
-        self.ntotal = 0
+        super().__init__(d, device, workspace_bytes)
 
-    def reset(self) -> None:
-        self._store = None
-        self._scale = None
-        self.ntotal = 0
+    def _columns(self) -> tuple:
+        return (("_store", (self.d,), torch.int8), ("_scale", (), torch.float32))
 
     @property
     def codes(self) -> torch.Tensor:
         """The stored codes, (ntotal, d) int8 (a view)."""
-        if self._store is None:
-            return torch.empty(0, self.d, dtype=torch.int8, device=self.device)
-        return self._store[: self.ntotal]
+        return self._view("_store")
 
     @property
     def scales(self) -> torch.Tensor:
         """The stored scales, (ntotal,) float32 (a view)."""
-        if self._scale is None:
-            return torch.empty(0, dtype=torch.float32, device=self.device)
-        return self._scale[: self.ntotal]
-
-    def reserve(self, n: int) -> None:
-        """Allocate room for n vectors in total, so that adding a corpus in chunks never copies it."""
-        if n > MAX_NTOTAL:
-            raise ValueError(f"Int8FlatIndex holds at most {MAX_NTOTAL} vectors")
-        cap = 0 if self._store is None else self._store.shape[0]
-        if n > cap:
-            grown = torch.empty(n, self.d, dtype=torch.int8, device=self.device)
-            gscale = torch.empty(n, dtype=torch.float32, device=self.device)
-            if self.ntotal:
-                grown[: self.ntotal].copy_(self._store[: self.ntotal])
-                gscale[: self.ntotal].copy_(self._scale[: self.ntotal])
-            self._store, self._scale = grown, gscale
+        return self._view("_scale")
 
     def _check_pair(self, pair):
         """A (codes int8 (n, d), scales float32 (n,)) tuple -> host-or-device tensors, shapes and dtypes checked."""
@@ -1182,9 +1175,10 @@ class Int8FlatIndex:
         return c, s
 
     def _check_rows(self, x) -> int:
-        if len(np.shape(x)) != 2 or np.shape(x)[1] != self.d:
-            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(x))}")
-        return int(np.shape(x)[0])
+        return super()._check_queries(x)
+
+    def _check_queries(self, queries) -> int:
+        return self._check_pair(queries)[0].shape[0] if _is_code_pair(queries) else self._check_rows(queries)
 
     def _quantize_into(self, x, codes: torch.Tensor, scales: torch.Tensor) -> None:
         """Float rows x (a tensor anywhere, an array or a memmap) -> the given device views, QUANTIZE_ROWS rows at a time: a host
@@ -1207,14 +1201,6 @@ class Int8FlatIndex:
             self._quantize_into(x, self._store[self.ntotal: self.ntotal + n], self._scale[self.ntotal: self.ntotal + n])
         self.ntotal += n
 
-    def batch_rows(self, M: int, k: int) -> int:
-        """The largest query batch (all of M, else halved down to a multiple of 128) whose workspace fits the bound."""
-        h = _C.lib()
-        m = M
-        while m > 128 and h.cx_search_int8_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
-            m = max(128, (m // 2) // 128 * 128)
-        return m
-
     def _query_codes(self, queries):
         """float rows or a (codes, scales) tuple -> (codes (M, d) int8, scales (M,) fp32) on the index's device."""
         if _is_code_pair(queries):
@@ -1231,51 +1217,14 @@ class Int8FlatIndex:
         missing entries are (-inf, -1).  queries: float rows (quantised per row) or a (codes, scales) tuple, as for add.
         exclude, below (a strict bound on the int8 score), nsplit: as FlatIPIndex.search.  numpy in -> numpy out, torch in ->
         torch out on the index's device."""
+        def prepare():
+            qc, qs = self._query_codes(queries)
+            D, ds = (self.codes.data_ptr(), self.scales.data_ptr()) if self.ntotal else (None, None)
+            return lambda h, b0, m, tail: _C.check(
+                h.cx_search_int8_topk(qc[b0].data_ptr(), D, qs[b0:].data_ptr(), ds, m, self.ntotal, self.d, self.d, self.d,
+                                      int(k), *tail), "cx_search_int8_topk")
         first = queries[0] if _is_code_pair(queries) else queries
-        as_numpy = not isinstance(first, torch.Tensor)
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-        if _is_code_pair(queries):
-            M = self._check_pair(queries)[0].shape[0]
-        else:
-            M = self._check_rows(queries)
-        xptr, xids = _exclusion_csr_host(exclude, M)
-        bel = None
-        if below is not None:
-            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
-            if bel.numel() != M:
-                raise ValueError(f"below has {bel.numel()} entries for {M} queries")
-            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-        qc, qs = self._query_codes(queries)
-        if xptr is not None:
-            xptr = xptr.to(self.device)
-            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
-        scores = torch.empty(M, k, dtype=torch.float32, device=self.device)
-        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
-        if M:
-            h = _C.lib()
-            with torch.cuda.device(self.device):
-                stream = _C.cur_stream()
-                mb = self.batch_rows(M, k)
-                ws = None
-                if self.ntotal:
-                    last = M - (M - 1) // mb * mb
-                    nbytes = max(h.cx_search_int8_ws_bytes(mb, self.ntotal, k, nsplit),
-                                 h.cx_search_int8_ws_bytes(last, self.ntotal, k, nsplit))
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                D, ds = self.codes, self.scales
-                for b0 in range(0, M, mb):
-                    m = min(mb, M - b0)
-                    _C.check(h.cx_search_int8_topk(qc[b0].data_ptr(), D.data_ptr() if self.ntotal else None,
-                                                   qs[b0:].data_ptr(), ds.data_ptr() if self.ntotal else None, m, self.ntotal,
-                                                   self.d, self.d, self.d, k,
-                                                   None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
-                                                   None if bel is None else bel[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
-                                                   scores[b0].data_ptr(), ids[b0].data_ptr(), stream), "cx_search_int8_topk")
-        if as_numpy:
-            return scores.cpu().numpy(), ids.cpu().numpy()
-        return scores, ids
+        return self._search_batched(queries, k, exclude, below, nsplit, not isinstance(first, torch.Tensor), prepare)
 
 
 def search_int8_rescored(index: Int8FlatIndex, vectors, queries, k: int, rescore_factor: int = 2, exclude=None, below=None):
@@ -1284,17 +1233,8 @@ def search_int8_rescored(index: Int8FlatIndex, vectors, queries, k: int, rescore
     or a memmap; see rescore).  queries: float rows.  exclude applies to the coarse stage, below to the exact score.
     -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit when the candidate lists cover the corpus.  Lists longer
     than the kernel's k bound (1024) are fetched in pages (_paged_candidates)."""
-    k = int(k)
-    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
-    as_numpy = not isinstance(queries, torch.Tensor)
-    M = index._check_rows(queries)
-    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
-    if below is not None and int(np.size(below)) != M:
-        raise ValueError(f"below has {int(np.size(below))} entries for {M} queries")
-    qd = _to_device_2d(queries, index.d, index.device)
-    qc = index._query_codes(queries)
-    cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
-    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+    return _search_rescored(index, vectors, queries, k, rescore_factor, exclude, below, lambda q, qd: index._query_codes(q),
+                            lambda qc, kp, ex: index.search(qc, kp, exclude=ex)[1])
 
 
 class IVFInt8Index(_IVFLists):
@@ -1384,23 +1324,12 @@ def search_ivf_int8_rescored(index: IVFInt8Index, vectors, queries, k: int, npro
     was made from, in add() order: device bf16 rows, a host array or a memmap; see rescore).  queries: float rows.  exclude
     applies to the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit
     when every list is probed and the candidate lists cover the corpus."""
-    k, nprobe = int(k), int(nprobe)
-    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
-    if not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
-        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
-    index._require_trained()
-    as_numpy = not isinstance(queries, torch.Tensor)
-    M = index._check_queries(queries)
-    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
-    if below is not None:
-        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
-        if n_below != M:
-            raise ValueError(f"below has {n_below} entries for {M} queries")
-    qd = _to_device_2d(queries, index.d, index.device)
-    qf = queries if isinstance(queries, torch.Tensor) else torch.from_numpy(np.array(queries, dtype=np.float32))
-    qf = _quantizable(qf.to(index.device))   # (once: a page of candidates quantises it again, to the same codes)
-    cand = _paged_candidates(lambda kp, ex: index.search(qf, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
-    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+    def floats(q, qd):   # (once: a page of candidates quantises them again, to the same codes)
+        q = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.array(q, dtype=np.float32))
+        return _quantizable(q.to(index.device))
+    nprobe = int(nprobe)
+    return _search_rescored(index, vectors, queries, k, rescore_factor, exclude, below, floats,
+                            lambda qf, kp, ex: index.search(qf, kp, nprobe, exclude=ex)[1], nprobe)
 
 
 PQ_KSUB = 256                    # centroids per sub-quantiser: a code is one byte
@@ -1532,7 +1461,7 @@ def pq_train_rows(n: int, sample: Optional[int], seed: int, first: int = PQ_KSUB
     return rows, torch.randperm(ns, generator=g)[:first]
 
 
-class PQFlatIndex:
+class PQFlatIndex(_FlatIndex):
     """Maximum-inner-product index over product-quantised rows on one GPU (faiss IndexPQ, 8 bits per sub-quantiser, asymmetric
     scoring): d / dsub bytes per vector -- with dsub = 8 what BinaryFlatIndex keeps -- where FlatIPIndex keeps 2 d.  A row is
     cut into m = d / dsub sub-vectors, each stored as the index of the nearest of 256 trained centroids; queries stay bf16.
@@ -1543,24 +1472,19 @@ class PQFlatIndex:
     Not here (IVF lists and residual encoding: IVFPQIndex): OPQ rotations, other code widths, a look-up-table scan, save / load (codebooks go
     in and out as arrays), more than one GPU."""
 
+    _ENTRY, _WS_BYTES = "cx_search_pq_topk", "cx_search_pq_ws_bytes"
+
     def __init__(self, d: int, dsub: int = 8, device="cuda", workspace_bytes: int = DEFAULT_WORKSPACE_BYTES, seed: int = 0):
         self.m = _check_pq_dims(int(d), int(dsub))
-        self.d, self.dsub = int(d), int(dsub)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("PQFlatIndex runs on the GPU (cx_search_pq_topk); there is no CPU path")
-        self.workspace_bytes = int(workspace_bytes)
+        super().__init__(d, device, workspace_bytes)
+        self.dsub = int(dsub)
         self.seed = int(seed)
         self._masters: Optional[torch.Tensor] = None   # (m, 256, dsub) fp32
         self._shadow: Optional[torch.Tensor] = None    # ... rounded to bf16: what encodes, decodes and scores
         self._hn: Optional[torch.Tensor] = None        # (m, 256) fp32 half norms of the shadow
-        self._store: Optional[torch.Tensor] = None     # (capacity, m) uint8; rows [0, ntotal) are the corpus
-        self.ntotal = 0
 
-    def reset(self) -> None:
-        """Drop the stored rows; the codebooks stay."""
-        self._store = None
-        self.ntotal = 0
+    def _columns(self) -> tuple:
+        return (("_store", (self.m,), torch.uint8),)
 
     @property
     def is_trained(self) -> bool:
@@ -1641,20 +1565,7 @@ class PQFlatIndex:
     @property
     def codes(self) -> torch.Tensor:
         """The stored codes, (ntotal, m) uint8 (a view)."""
-        if self._store is None:
-            return torch.empty(0, self.m, dtype=torch.uint8, device=self.device)
-        return self._store[: self.ntotal]
-
-    def reserve(self, n: int) -> None:
-        """Allocate room for n codes in total, so that adding a corpus in chunks never copies it."""
-        if n > MAX_NTOTAL:
-            raise ValueError(f"PQFlatIndex holds at most {MAX_NTOTAL} vectors")
-        cap = 0 if self._store is None else self._store.shape[0]
-        if n > cap:
-            grown = torch.empty(n, self.m, dtype=torch.uint8, device=self.device)
-            if self.ntotal:
-                grown[: self.ntotal].copy_(self._store[: self.ntotal])
-            self._store = grown
+        return self._view("_store")
 
     def _is_codes(self, x) -> bool:
         return (x.dtype == torch.uint8) if isinstance(x, torch.Tensor) else (np.asarray(x).dtype == np.uint8)
@@ -1699,63 +1610,18 @@ class PQFlatIndex:
         s = torch.arange(self.m, device=self.device)[None, :]
         return self._shadow[s, codes.to(torch.int64)].reshape(codes.shape[0], self.d)
 
-    def batch_rows(self, M: int, k: int) -> int:
-        """The largest query batch (all of M, else halved down to a multiple of 128) whose workspace fits the bound."""
-        h = _C.lib()
-        m = M
-        while m > 128 and h.cx_search_pq_ws_bytes(m, max(self.ntotal, 1), k, 0) > self.workspace_bytes:
-            m = max(128, (m // 2) // 128 * 128)
-        return m
-
     def search(self, queries, k: int, exclude=None, below=None, nsplit: int = 0):
         """-> (scores (M, k) float32, ids (M, k) int64): FlatIPIndex.search over the decoded rows, bit for bit -- per query the k
         largest inner products of the bf16 query with the decoded vectors, descending, ties to the lower id; missing entries are
         (-inf, -1).  exclude, below, nsplit, numpy in -> numpy out: as FlatIPIndex.search."""
-        as_numpy = not isinstance(queries, torch.Tensor)
-        k = int(k)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-        if len(np.shape(queries)) != 2 or np.shape(queries)[1] != self.d:
-            raise ValueError(f"expected a (n, {self.d}) array, got shape {tuple(np.shape(queries))}")
-        M = int(np.shape(queries)[0])
-        xptr, xids = _exclusion_csr_host(exclude, M)
-        if below is not None:
-            n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
-            if n_below != M:
-                raise ValueError(f"below has {n_below} entries for {M} queries")
-        self._require_trained()
-        bel = None
-        if below is not None:
-            bel = torch.as_tensor(np.asarray(below) if not isinstance(below, torch.Tensor) else below)
-            bel = bel.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
-        q = _to_device_2d(queries, self.d, self.device)
-        if xptr is not None:
-            xptr = xptr.to(self.device)
-            xids = (xids if xids.numel() else torch.zeros(1, dtype=torch.int64)).to(self.device)
-        scores = torch.empty(M, k, dtype=torch.float32, device=self.device)
-        ids = torch.empty(M, k, dtype=torch.int64, device=self.device)
-        if M:
-            h = _C.lib()
-            with torch.cuda.device(self.device):
-                stream = _C.cur_stream()
-                mb = self.batch_rows(M, k)
-                ws = None
-                if self.ntotal:
-                    last = M - (M - 1) // mb * mb
-                    nbytes = max(h.cx_search_pq_ws_bytes(mb, self.ntotal, k, nsplit),
-                                 h.cx_search_pq_ws_bytes(last, self.ntotal, k, nsplit))
-                    ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                D = self.codes
-                for b0 in range(0, M, mb):
-                    m = min(mb, M - b0)
-                    _C.check(h.cx_search_pq_topk(q[b0].data_ptr(), D.data_ptr() if self.ntotal else None,
-                                                 self._shadow.data_ptr(), m, self.ntotal, self.d, self.dsub, self.d, self.m, k,
-                                                 None if xptr is None else xptr[b0:].data_ptr(), _C.ptr(xids),
-                                                 None if bel is None else bel[b0:].data_ptr(), int(nsplit), _C.ptr(ws),
-                                                 scores[b0].data_ptr(), ids[b0].data_ptr(), stream), "cx_search_pq_topk")
-        if as_numpy:
-            return scores.cpu().numpy(), ids.cpu().numpy()
-        return scores, ids
+        def prepare():
+            self._require_trained()
+            q = _to_device_2d(queries, self.d, self.device)
+            D = self.codes.data_ptr() if self.ntotal else None
+            return lambda h, b0, m, tail: _C.check(
+                h.cx_search_pq_topk(q[b0].data_ptr(), D, self._shadow.data_ptr(), m, self.ntotal, self.d, self.dsub, self.d,
+                                    self.m, int(k), *tail), "cx_search_pq_topk")
+        return self._search_batched(queries, k, exclude, below, nsplit, not isinstance(queries, torch.Tensor), prepare)
 
 
 def search_pq_rescored(index: PQFlatIndex, vectors, queries, k: int, rescore_factor: int = 4, exclude=None, below=None):
@@ -1764,21 +1630,8 @@ def search_pq_rescored(index: PQFlatIndex, vectors, queries, k: int, rescore_fac
     a memmap; see rescore).  queries: float rows.  exclude applies to the coarse stage, below to the exact score.
     -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit when the candidate lists cover the corpus.  Lists longer
     than the kernel's k bound (1024) are fetched in pages (_paged_candidates)."""
-    k = int(k)
-    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
-    as_numpy = not isinstance(queries, torch.Tensor)
-    if len(np.shape(queries)) != 2 or np.shape(queries)[1] != index.d:
-        raise ValueError(f"expected a (n, {index.d}) array, got shape {tuple(np.shape(queries))}")
-    M = int(np.shape(queries)[0])
-    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
-    if below is not None:
-        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
-        if n_below != M:
-            raise ValueError(f"below has {n_below} entries for {M} queries")
-    index._require_trained()
-    qd = _to_device_2d(queries, index.d, index.device)
-    cand = _paged_candidates(lambda kp, ex: index.search(qd, kp, exclude=ex)[1], M, c, index.ntotal, exclude)
-    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+    return _search_rescored(index, vectors, queries, k, rescore_factor, exclude, below, lambda q, qd: qd,
+                            lambda qc, kp, ex: index.search(qc, kp, exclude=ex)[1])
 
 
 class IVFPQIndex(_IVFLists):
@@ -1953,21 +1806,9 @@ def search_ivf_pq_rescored(index: IVFPQIndex, vectors, queries, k: int, nprobe: 
     from, in add() order: device bf16 rows, a host array or a memmap; see rescore).  queries: float rows.  exclude applies to
     the coarse stage, below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it bit for bit when every
     list is probed and the candidate lists cover the corpus."""
-    k, nprobe = int(k), int(nprobe)
-    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
-    if not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
-        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
-    index._require_trained()
-    as_numpy = not isinstance(queries, torch.Tensor)
-    M = index._check_queries(queries)
-    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
-    if below is not None:
-        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
-        if n_below != M:
-            raise ValueError(f"below has {n_below} entries for {M} queries")
-    qd = _to_device_2d(queries, index.d, index.device)
-    cand = _paged_candidates(lambda kp, ex: index.search(qd, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
-    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+    nprobe = int(nprobe)
+    return _search_rescored(index, vectors, queries, k, rescore_factor, exclude, below, lambda q, qd: qd,
+                            lambda qc, kp, ex: index.search(qc, kp, nprobe, exclude=ex)[1], nprobe)
 
 
 def _is_codes(x) -> bool:
@@ -1990,6 +1831,9 @@ class IVFBinaryIndex(_IVFLists):
     arrays), more than one GPU."""
 
     _ENTRY = "cx_search_hamming_window_topk"
+    _WS_BYTES, _MERGE = "cx_search_hamming_window_ws_bytes", "cx_hamming_merge_lists"
+    _BOUND = ("max_dist", torch.int32)
+    _LIST = (torch.int32, 2 ** 31 - 1)
 
     @property
     def centroids(self) -> torch.Tensor:
@@ -2101,67 +1945,32 @@ class IVFBinaryIndex(_IVFLists):
     def _pair_row_bytes(self) -> int:
         return self.d // 8 + 4
 
+    def _check_queries(self, queries) -> int:
+        return self._check_rows(queries)[0]
+
+    def _prepare_queries(self, queries):
+        M, codes = self._check_rows(queries)
+        parts = list(self._code_chunks(queries, M, codes))
+        if not parts:    # (no queries)
+            parts = [torch.empty(0, self.d // 8, dtype=torch.uint8, device=self.device)]
+        qc = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return qc, qc   # the codes probe the centroid codes and are what the scan gathers
+
+    def _scan(self, h, qc, b0, m, pair_q, k, mid, end, pptr, pids, mg, bias, ws, ls, li, stream) -> None:
+        qg = qc[b0: b0 + m][pair_q]
+        nb = self.d // 8
+        _C.check(h.cx_search_hamming_window_topk(qg.data_ptr(), self._cols[0].data_ptr(), pair_q.numel(), self.ntotal, self.d,
+                                                 nb, nb, k, mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
+                                                 _C.ptr(mg), ws.data_ptr(), ls.data_ptr(), li.data_ptr(), stream),
+                 "cx_search_hamming_window_topk")
+
     def search(self, queries, k: int, nprobe: int, exclude=None, max_dist=None):
         """-> (dist (M, k) int32, ids (M, k) int64), the conventions of BinaryFlatIndex.search (ascending distance, ties to the
         lower id, (INT32_MAX, -1) where the probed lists hold fewer than k admissible rows; numpy in -> numpy out) over the rows
         of the nprobe lists whose centroid codes are nearest to each query, 1 <= nprobe <= min(nlist, 256).  queries: float
         rows or uint8 codes, as for add.  ids, and the ids of exclude, are the ids add() gave; max_dist is inclusive.
         nprobe == nlist is BinaryFlatIndex.search, bit for bit."""
-        as_numpy = not isinstance(queries, torch.Tensor)
-        k, nprobe = int(k), int(nprobe)
-        if not 1 <= k <= MAX_K:
-            raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
-        if not 1 <= nprobe <= min(self.nlist, MAX_NPROBE):
-            raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(self.nlist, MAX_NPROBE)}], got {nprobe}")
-        self._require_trained()
-        M, codes = self._check_rows(queries)
-        row_ptr, xhost = _exclusion_csr_host(exclude, M)
-        md = None
-        if max_dist is not None:
-            md = torch.as_tensor(np.asarray(max_dist) if not isinstance(max_dist, torch.Tensor) else max_dist)
-            if md.numel() != M:
-                raise ValueError(f"max_dist has {md.numel()} entries for {M} queries")
-            md = md.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
-        dist = torch.full((M, k), 2 ** 31 - 1, dtype=torch.int32, device=self.device)
-        ids = torch.full((M, k), -1, dtype=torch.int64, device=self.device)
-        if M and self.ntotal:
-            self._finalise()
-            h = _C.lib()
-            nb = self.d // 8
-            parts = list(self._code_chunks(queries, M, codes))
-            qc = parts[0] if len(parts) == 1 else torch.cat(parts)
-            D = self._cols[0]
-            with torch.cuda.device(self.device):
-                stream = _C.cur_stream()
-                probes = self._coarse.search(qc, nprobe)[1]
-                dptr = xids = None
-                if row_ptr is not None and xhost.numel():
-                    dptr, xids = row_ptr.to(self.device), xhost.to(self.device)
-                mq = self.batch_queries(M, k, nprobe)
-                for b0 in range(0, M, mq):
-                    m = min(mq, M - b0)
-                    P = m * nprobe
-                    pair_q, mid, end, src = ivf_pair_plan(probes[b0: b0 + m], self._list_ptr)
-                    mg = None if md is None else md[b0: b0 + m][pair_q]
-                    pptr = pids = None
-                    if dptr is not None:
-                        e0, e1 = int(row_ptr[b0]), int(row_ptr[b0 + m])      # (host copies)
-                        if e1 > e0:
-                            pptr, pids = ivf_pair_exclusions(dptr[b0: b0 + m + 1] - e0, xids[e0: e1], pair_q, self._inv, nprobe)
-                    ws = torch.empty(h.cx_search_hamming_window_ws_bytes(P, k), dtype=torch.uint8, device=self.device)
-                    ls = torch.empty(P, k, dtype=torch.int32, device=self.device)
-                    li = torch.empty(P, k, dtype=torch.int64, device=self.device)
-                    qg = qc[b0: b0 + m][pair_q]
-                    _C.check(h.cx_search_hamming_window_topk(qg.data_ptr(), D.data_ptr(), P, self.ntotal, self.d, nb, nb, k,
-                                                             mid.data_ptr(), end.data_ptr(), _C.ptr(pptr), _C.ptr(pids),
-                                                             _C.ptr(mg), ws.data_ptr(), ls.data_ptr(), li.data_ptr(), stream),
-                             "cx_search_hamming_window_topk")
-                    _C.check(h.cx_hamming_merge_lists(ls.data_ptr(), li.data_ptr(), P, k, src.data_ptr(), m, nprobe,
-                                                      self._order.data_ptr(), self.ntotal, dist[b0].data_ptr(),
-                                                      ids[b0].data_ptr(), stream), "cx_hamming_merge_lists")
-        if as_numpy:
-            return dist.cpu().numpy(), ids.cpu().numpy()
-        return dist, ids
+        return super().search(queries, k, nprobe, exclude=exclude, below=max_dist)
 
 
 def search_ivf_binary_rescored(index: IVFBinaryIndex, vectors, queries, k: int, nprobe: int, rescore_factor: int = 4,
@@ -2172,24 +1981,11 @@ def search_ivf_binary_rescored(index: IVFBinaryIndex, vectors, queries, k: int, 
     refused: the exact stage needs the floats), binarised by sign for the coarse stage.  exclude applies to the coarse stage,
     below to the exact score.  -> (scores, ids) as FlatIPIndex.search; equal to it over the rows of the probed lists when
     the candidate lists cover them."""
-    k, nprobe = int(k), int(nprobe)
-    c = _check_rescored_arguments(index, vectors, k, rescore_factor)
-    if not 1 <= nprobe <= min(index.nlist, MAX_NPROBE):
-        raise ValueError(f"nprobe must be in [1, min(nlist, {MAX_NPROBE})] = [1, {min(index.nlist, MAX_NPROBE)}], got {nprobe}")
-    index._require_trained()
     if _is_codes(queries):
         raise ValueError("search_ivf_binary_rescored takes float queries, not codes")
-    as_numpy = not isinstance(queries, torch.Tensor)
-    M = index._check_rows(queries)[0]
-    _exclusion_csr_host(exclude, M)   # (malformed filters raise before any launch)
-    if below is not None:
-        n_below = below.numel() if isinstance(below, torch.Tensor) else int(np.size(below))
-        if n_below != M:
-            raise ValueError(f"below has {n_below} entries for {M} queries")
-    qd = _to_device_2d(queries, index.d, index.device)
-    qc = pack_sign_bits(qd)
-    cand = _paged_candidates(lambda kp, ex: index.search(qc, kp, nprobe, exclude=ex)[1], M, c, index.ntotal, exclude)
-    return _rescore_candidates(qd, cand, vectors, k, below, index.device, as_numpy)
+    nprobe = int(nprobe)
+    return _search_rescored(index, vectors, queries, k, rescore_factor, exclude, below, lambda q, qd: pack_sign_bits(qd),
+                            lambda qc, kp, ex: index.search(qc, kp, nprobe, exclude=ex)[1], nprobe)
 
 
 def encode(model, texts: Sequence[str], tokenizer, batch_size: int = 256, max_length: int = 512,
