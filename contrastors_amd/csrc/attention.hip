@@ -1411,6 +1411,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_s128v_kernel(AttnParams p) {
 
 #include "attn_s256.inc"
 #include "attn_long.inc"
+#include "attn_window.inc"
 
 #ifndef CX_PRODUCT
 int g_fwd_s128 = 2;  // cx_attn_set_fwd_s128: non-zero = the single-pass kernels for max_seqlen <= 128 / <= 256 (default), 0 = the general streaming kernel (A/B, tests)
@@ -1686,6 +1687,46 @@ int cx_attn_varlen_kvpacked_bwd(const uint16_t* dout, const uint16_t* q, const u
     if (max_seqlen_k > 0)
         hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, dim3((max_seqlen_k + 127) / 128, H, B), dim3(256), 0,
                            (hipStream_t)stream, p);
+    return done();
+}
+
+// Sliding-window (local) self-attention (flash_attn_*_qkvpacked_func(window_size = (left, right))): the banded kernels of
+// attn_window.inc for any max_seqlen; -1 = unbounded on that side.  No rotary tables, no dropout.
+static bool window_sides(int left, int right, int max_seqlen, int* wl, int* wr) {
+    if (left < -1 || right < -1 || max_seqlen >= WIN_INF) return false;
+    *wl = left < 0 || left > WIN_INF ? WIN_INF : left;
+    *wr = right < 0 || right > WIN_INF ? WIN_INF : right;
+    return true;
+}
+
+int cx_attn_varlen_window_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, uint16_t* out, float* lse, int B, int H, int T,
+                              int max_seqlen, int window_left, int window_right, float softmax_scale, void* stream) {
+    int wl, wr;
+    if (!window_sides(window_left, window_right, max_seqlen, &wl, &wr)) return CX_ERR_ARG;
+    if (B <= 0 || T <= 0 || max_seqlen <= 0) return CX_OK;
+    if (!qkv || !cu_seqlens || !out || !lse || H <= 0) return CX_ERR_ARG;
+    AttnParams p = {};
+    p.qkv = qkv; p.cu = cu_seqlens; p.out = out; p.lse = lse;
+    p.H = H; p.T = T; p.scale = softmax_scale;
+    hipLaunchKernelGGL(attn_fwd_window_kernel, dim3((max_seqlen + 127) / 128, H, B), dim3(256), LONG_LDS, (hipStream_t)stream, p, wl, wr);
+    return done();
+}
+
+int cx_attn_varlen_window_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
+                              const int32_t* cu_seqlens, float* delta, uint16_t* dqkv, int B, int H, int T, int max_seqlen,
+                              int window_left, int window_right, float softmax_scale, void* stream) {
+    int wl, wr;
+    if (!window_sides(window_left, window_right, max_seqlen, &wl, &wr)) return CX_ERR_ARG;
+    if (B <= 0 || T <= 0 || max_seqlen <= 0) return CX_OK;
+    if (!dout || !qkv || !out || !lse || !cu_seqlens || !delta || !dqkv || H <= 0) return CX_ERR_ARG;
+    AttnParams p = {};
+    p.qkv = qkv; p.cu = cu_seqlens;
+    p.out = const_cast<uint16_t*>(out); p.lse = const_cast<float*>(lse);
+    p.dout = dout; p.delta = delta; p.dqkv = dqkv;
+    p.H = H; p.T = T; p.scale = softmax_scale;
+    const dim3 grid((max_seqlen + 127) / 128, H, B);
+    hipLaunchKernelGGL(attn_bwd_dq_window_kernel, grid, dim3(256), LONG_LDS, (hipStream_t)stream, p, wl, wr);
+    hipLaunchKernelGGL(attn_bwd_dkv_window_kernel, grid, dim3(256), LONG_LDS_DKV, (hipStream_t)stream, p, wl, wr);
     return done();
 }
 

@@ -24,7 +24,7 @@ def _draw_philox(device):
 
 class _VarlenQKVPacked(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen, scale, dropout_p=0.0):
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, scale, dropout_p=0.0, window=None):
         if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] != 64:
             raise NotImplementedError("qkv must be bf16 (T,3,H,64)")
         qkv = qkv.contiguous()
@@ -34,7 +34,11 @@ class _VarlenQKVPacked(torch.autograd.Function):
         out = torch.empty(T, H, D, dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
         rng = None
-        if dropout_p:
+        if window is not None:  # a finite window: the banded kernels (no dropout, _window_of refused it)
+            _C.check(_C.lib().cx_attn_varlen_window_fwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), B, H, T,
+                                                        int(max_seqlen), window[0], window[1], scale, _C.cur_stream()),
+                     "attn fwd (window)")
+        elif dropout_p:
             rng = _draw_philox(qkv.device)
             _C.check(_C.lib().cx_attn_varlen_dropout_fwd(qkv.data_ptr(), cu.data_ptr(), None, None, out.data_ptr(),
                                                          lse.data_ptr(), B, H, T, int(max_seqlen), scale, float(dropout_p),
@@ -43,17 +47,21 @@ class _VarlenQKVPacked(torch.autograd.Function):
             _C.check(_C.lib().cx_attn_varlen_fwd(qkv.data_ptr(), cu.data_ptr(), None, None, out.data_ptr(), lse.data_ptr(),
                                                  B, H, T, int(max_seqlen), scale, _C.cur_stream()), "attn fwd")
         ctx.save_for_backward(qkv, out, lse, cu)
-        ctx.meta = (B, H, T, int(max_seqlen), scale, float(dropout_p), rng)
+        ctx.meta = (B, H, T, int(max_seqlen), scale, float(dropout_p), rng, window)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse, cu = ctx.saved_tensors
-        B, H, T, mx, scale, p_drop, rng = ctx.meta
+        B, H, T, mx, scale, p_drop, rng, window = ctx.meta
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         delta = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
-        if p_drop:
+        if window is not None:
+            _C.check(_C.lib().cx_attn_varlen_window_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                        cu.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), B, H, T, mx, window[0],
+                                                        window[1], scale, _C.cur_stream()), "attn bwd (window)")
+        elif p_drop:
             _C.check(_C.lib().cx_attn_varlen_dropout_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                          cu.data_ptr(), None, None, delta.data_ptr(), dqkv.data_ptr(), B, H, T,
                                                          mx, scale, p_drop, rng[0], rng[1], 0, _C.cur_stream()),
@@ -62,7 +70,28 @@ class _VarlenQKVPacked(torch.autograd.Function):
             _C.check(_C.lib().cx_attn_varlen_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                  cu.data_ptr(), None, None, delta.data_ptr(), dqkv.data_ptr(), B, H, T, mx,
                                                  scale, _C.cur_stream()), "attn bwd")
-        return dqkv, None, None, None, None
+        return dqkv, None, None, None, None, None
+
+
+def _window_of(window_size, max_seqlen, dropout_p):
+    """flash-attn's window_size = (left, right), -1 = unbounded: query i sees the keys i - left .. i + right of its own sequence.
+    None when the window covers every pair of a sequence of max_seqlen rows (today's kernels, unchanged), else (left, right)."""
+    left, right = (int(w) for w in window_size)
+    if left < -1 or right < -1:
+        raise ValueError("window_size: each side is -1 (unbounded) or >= 0")
+    if all(w < 0 or w >= int(max_seqlen) - 1 for w in (left, right)):
+        return None
+    if dropout_p:
+        raise NotImplementedError("attention dropout > 0 with a finite window_size is not built")
+    return left, right
+
+
+def _no_window(window_size):
+    left, right = (int(w) for w in window_size)
+    if left < -1 or right < -1:
+        raise ValueError("window_size: each side is -1 (unbounded) or >= 0")
+    if left >= 0 or right >= 0:
+        raise NotImplementedError("a finite window_size is built for the qkv-packed self-attention forms only")
 
 
 def _check(dropout_p, causal, return_attn_probs, dropout_ok=False):
@@ -80,7 +109,8 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
                                      window_size=(-1, -1), alibi_slopes=None, deterministic=False,
                                      return_attn_probs=False):
     _check(dropout_p, causal, return_attn_probs, dropout_ok=True)
-    return _VarlenQKVPacked.apply(qkv, cu_seqlens, max_seqlen, _scale(softmax_scale, qkv.shape[-1]), float(dropout_p))
+    return _VarlenQKVPacked.apply(qkv, cu_seqlens, max_seqlen, _scale(softmax_scale, qkv.shape[-1]), float(dropout_p),
+                                  _window_of(window_size, max_seqlen, dropout_p))
 
 
 def flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
@@ -90,7 +120,7 @@ def flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=Fal
     B, S = qkv.shape[:2]
     cu = torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=qkv.device)
     out = _VarlenQKVPacked.apply(qkv.reshape(B * S, *qkv.shape[2:]), cu, S, _scale(softmax_scale, qkv.shape[-1]),
-                                 float(dropout_p))
+                                 float(dropout_p), _window_of(window_size, S, dropout_p))
     return out.view(B, S, *out.shape[1:])
 
 
@@ -140,6 +170,7 @@ def flash_attn_varlen_kvpacked_func(q, kv, cu_seqlens_q, cu_seqlens_k, max_seqle
                                     deterministic=False, return_attn_probs=False):
     """(Tq,H,64) x (Tk,2,H,64) -> (Tq,H,64): FlashAttentionPooling's varlen branch (sc/layers/attention.py:391-419)."""
     _check(dropout_p, causal, return_attn_probs)
+    _no_window(window_size)
     return _VarlenKVPacked.apply(q, kv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
                                  _scale(softmax_scale, q.shape[-1]))
 
@@ -148,6 +179,7 @@ def flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=Fa
                              alibi_slopes=None, deterministic=False, return_attn_probs=False):
     """(B,Sq,H,64) x (B,Sk,2,H,64) -> (B,Sq,H,64): FlashAttentionPooling's fixed-length branch (attention.py:420-428)."""
     _check(dropout_p, causal, return_attn_probs)
+    _no_window(window_size)
     B, Sq = q.shape[:2]
     Sk = kv.shape[1]
     cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)

@@ -323,6 +323,15 @@ int cx_attn_varlen_kvpacked_bwd(const uint16_t* dout, const uint16_t* q, const u
                                 const float* lse, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, float* delta,
                                 uint16_t* dq, uint16_t* dkv, int B, int H, int Tq, int max_seqlen_q, int max_seqlen_k,
                                 float softmax_scale, void* stream);
+/* sliding-window (local) self-attention, flash_attn_*_qkvpacked_func(window_size = (left, right)): query i of a sequence
+ * attends key j of the same sequence iff i - left <= j <= i + right; -1 = unbounded on that side, anything below is
+ * CX_ERR_ARG.  Layouts as cx_attn_varlen_fwd/_bwd, any max_seqlen, no rotary tables, no dropout; work is proportional to
+ * T * (left + right).  bwd: delta is written by the dQ kernel, dqkv fully overwritten. */
+int cx_attn_varlen_window_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, uint16_t* out, float* lse, int B, int H, int T,
+                              int max_seqlen, int window_left, int window_right, float softmax_scale, void* stream);
+int cx_attn_varlen_window_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
+                              const int32_t* cu_seqlens, float* delta, uint16_t* dqkv, int B, int H, int T, int max_seqlen,
+                              int window_left, int window_right, float softmax_scale, void* stream);
 /* standalone K11 (apply_rotary_emb_func on a packed qkv, in place on q and k; sign=-1 gives the backward). */
 int cx_rotary_qkv_inplace(uint16_t* qkv, const int32_t* cu_seqlens, const float* rot_cos, const float* rot_sin,
                           int B, int H, int T, int max_seqlen, int sign, void* stream);
