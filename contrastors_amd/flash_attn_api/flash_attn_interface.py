@@ -25,8 +25,13 @@ def _draw_philox(device):
 class _VarlenQKVPacked(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, cu_seqlens, max_seqlen, scale, dropout_p=0.0, window=None):
-        if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] != 64:
-            raise NotImplementedError("qkv must be bf16 (T,3,H,64)")
+        if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] not in (32, 64):
+            raise NotImplementedError("qkv must be bf16 (T,3,H,D) with head_dim D = 32 or 64")
+        d32 = qkv.shape[3] == 32  # the head-pair kernels of csrc/attn_d32.hip
+        if d32 and dropout_p:
+            raise NotImplementedError("attention dropout > 0 at head_dim 32 is not built")
+        if d32 and window is not None:
+            raise NotImplementedError("a finite window_size at head_dim 32 is not built")
         qkv = qkv.contiguous()
         T, _, H, D = qkv.shape
         B = cu_seqlens.numel() - 1
@@ -34,7 +39,10 @@ class _VarlenQKVPacked(torch.autograd.Function):
         out = torch.empty(T, H, D, dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
         rng = None
-        if window is not None:  # a finite window: the banded kernels (no dropout, _window_of refused it)
+        if d32:
+            _C.check(_C.lib().cx_attn_varlen_d32_fwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), B, H, T,
+                                                     int(max_seqlen), scale, _C.cur_stream()), "attn fwd (head_dim 32)")
+        elif window is not None:  # a finite window: the banded kernels (no dropout, _window_of refused it)
             _C.check(_C.lib().cx_attn_varlen_window_fwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), B, H, T,
                                                         int(max_seqlen), window[0], window[1], scale, _C.cur_stream()),
                      "attn fwd (window)")
@@ -57,7 +65,11 @@ class _VarlenQKVPacked(torch.autograd.Function):
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         delta = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
-        if window is not None:
+        if qkv.shape[3] == 32:
+            _C.check(_C.lib().cx_attn_varlen_d32_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                     cu.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), B, H, T, mx, scale,
+                                                     _C.cur_stream()), "attn bwd (head_dim 32)")
+        elif window is not None:
             _C.check(_C.lib().cx_attn_varlen_window_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                         cu.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), B, H, T, mx, window[0],
                                                         window[1], scale, _C.cur_stream()), "attn bwd (window)")
@@ -115,7 +127,7 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
 
 def flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
                               alibi_slopes=None, deterministic=False, return_attn_probs=False):
-    """(B,S,3,H,64) fixed-length form (the ViT path, attention.py:220-226): same kernel, cu_seqlens = arange * S."""
+    """(B,S,3,H,64 or 32) fixed-length form (the ViT path, attention.py:220-226): same kernel, cu_seqlens = arange * S."""
     _check(dropout_p, causal, return_attn_probs, dropout_ok=True)
     B, S = qkv.shape[:2]
     cu = torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=qkv.device)
@@ -129,6 +141,8 @@ class _VarlenKVPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, cu_q, cu_k, max_q, max_k, scale):
+        if q.dim() == 3 and q.shape[2] == 32:
+            raise NotImplementedError("head_dim 32 is built for the qkv-packed self-attention forms only (kv-packed: 64)")
         if q.dtype != torch.bfloat16 or q.dim() != 3 or q.shape[2] != 64:
             raise NotImplementedError("q must be bf16 (Tq,H,64)")
         if kv.dtype != torch.bfloat16 or kv.dim() != 4 or kv.shape[1] != 2 or kv.shape[3] != 64:

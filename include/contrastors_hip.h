@@ -332,6 +332,16 @@ int cx_attn_varlen_window_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, ui
 int cx_attn_varlen_window_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
                               const int32_t* cu_seqlens, float* delta, uint16_t* dqkv, int B, int H, int T, int max_seqlen,
                               int window_left, int window_right, float softmax_scale, void* stream);
+/* self-attention at head_dim 32, flash_attn_*_qkvpacked_func on (.., 3, H, 32) (csrc/attn_d32.hip): qkv:(T,3,H,32) bf16,
+ * out / dout:(T,H,32) bf16, lse / delta:(H,T) fp32.  Conventions of cx_attn_varlen_window_fwd/_bwd without a window: any
+ * max_seqlen, any H >= 1 (a workgroup serves a head pair; the last head of an odd H alone, touching only its own 64 bytes
+ * of a row), no rotary tables, no dropout.  bwd: delta is written by the dQ kernel, dqkv fully overwritten, no atomics (the
+ * same bits every run).  Additive: cx_abi_version stays as it is. */
+int cx_attn_varlen_d32_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, uint16_t* out, float* lse, int B, int H, int T,
+                           int max_seqlen, float softmax_scale, void* stream);
+int cx_attn_varlen_d32_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
+                           const int32_t* cu_seqlens, float* delta, uint16_t* dqkv, int B, int H, int T, int max_seqlen,
+                           float softmax_scale, void* stream);
 /* standalone K11 (apply_rotary_emb_func on a packed qkv, in place on q and k; sign=-1 gives the backward). */
 int cx_rotary_qkv_inplace(uint16_t* qkv, const int32_t* cu_seqlens, const float* rot_cos, const float* rot_sin,
                           int B, int H, int T, int max_seqlen, int sign, void* stream);
