@@ -147,6 +147,8 @@ _SIGS = {
     "cx_attn_varlen_kvpacked_bwd": (i32, [vp] * 10 + [i32, i32, i32, i32, i32, f32, vp]),
     "cx_attn_varlen_window_fwd": (i32, [vp] * 4 + [i32, i32, i32, i32, i32, i32, f32, vp]),
     "cx_attn_varlen_window_bwd": (i32, [vp] * 7 + [i32, i32, i32, i32, i32, i32, f32, vp]),
+    "cx_attn_varlen_alibi_fwd": (i32, [vp] * 3 + [i32, vp, vp, i32, i32, i32, i32, f32, vp]),
+    "cx_attn_varlen_alibi_bwd": (i32, [vp] * 6 + [i32, vp, vp, i32, i32, i32, i32, f32, vp]),
     "cx_attn_varlen_d32_fwd": (i32, [vp] * 4 + [i32, i32, i32, i32, f32, vp]),
     "cx_attn_varlen_d32_bwd": (i32, [vp] * 7 + [i32, i32, i32, i32, f32, vp]),
     "cx_rotary_qkv_inplace": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),

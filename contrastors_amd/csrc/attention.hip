@@ -1412,6 +1412,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_s128v_kernel(AttnParams p) {
 #include "attn_s256.inc"
 #include "attn_long.inc"
 #include "attn_window.inc"
+#include "attn_alibi.inc"
 
 #ifndef CX_PRODUCT
 int g_fwd_s128 = 2;  // cx_attn_set_fwd_s128: non-zero = the single-pass kernels for max_seqlen <= 128 / <= 256 (default), 0 = the general streaming kernel (A/B, tests)
@@ -1727,6 +1728,44 @@ int cx_attn_varlen_window_bwd(const uint16_t* dout, const uint16_t* qkv, const u
     const dim3 grid((max_seqlen + 127) / 128, H, B);
     hipLaunchKernelGGL(attn_bwd_dq_window_kernel, grid, dim3(256), LONG_LDS, (hipStream_t)stream, p, wl, wr);
     hipLaunchKernelGGL(attn_bwd_dkv_window_kernel, grid, dim3(256), LONG_LDS_DKV, (hipStream_t)stream, p, wl, wr);
+    return done();
+}
+
+// Self-attention with ALiBi (flash_attn_*_qkvpacked_func(alibi_slopes = ...)): the kernels of attn_alibi.inc for any
+// max_seqlen below 2^24 (row distances are formed exactly in fp32).  slopes: fp32 (H,) with slopes_batch_stride 0 or (B, H)
+// with slopes_batch_stride H, finite and >= 0 (not checked here).  No rotary tables, no dropout.
+static bool alibi_args(const float* slopes, int slopes_batch_stride, int H, int max_seqlen, float softmax_scale) {
+    return slopes && (slopes_batch_stride == 0 || slopes_batch_stride == H) && softmax_scale > 0.f && max_seqlen < (1 << 24);
+}
+
+int cx_attn_varlen_alibi_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, int slopes_batch_stride,
+                             uint16_t* out, float* lse, int B, int H, int T, int max_seqlen, float softmax_scale, void* stream) {
+    if (!alibi_args(slopes, slopes_batch_stride, H, max_seqlen, softmax_scale)) return CX_ERR_ARG;
+    if (B <= 0 || T <= 0 || max_seqlen <= 0) return CX_OK;
+    if (!qkv || !cu_seqlens || !out || !lse || H <= 0) return CX_ERR_ARG;
+    AttnParams p = {};
+    p.qkv = qkv; p.cu = cu_seqlens; p.out = out; p.lse = lse;
+    p.H = H; p.T = T; p.scale = softmax_scale;
+    hipLaunchKernelGGL(attn_fwd_alibi_kernel, dim3((max_seqlen + 255) / 256, H, B), dim3(256), LONG_LDS, (hipStream_t)stream, p, slopes,
+                       slopes_batch_stride);
+    return done();
+}
+
+int cx_attn_varlen_alibi_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
+                             const int32_t* cu_seqlens, const float* slopes, int slopes_batch_stride, float* delta,
+                             uint16_t* dqkv, int B, int H, int T, int max_seqlen, float softmax_scale, void* stream) {
+    if (!alibi_args(slopes, slopes_batch_stride, H, max_seqlen, softmax_scale)) return CX_ERR_ARG;
+    if (B <= 0 || T <= 0 || max_seqlen <= 0) return CX_OK;
+    if (!dout || !qkv || !out || !lse || !cu_seqlens || !delta || !dqkv || H <= 0) return CX_ERR_ARG;
+    AttnParams p = {};
+    p.qkv = qkv; p.cu = cu_seqlens;
+    p.out = const_cast<uint16_t*>(out); p.lse = const_cast<float*>(lse);
+    p.dout = dout; p.delta = delta; p.dqkv = dqkv;
+    p.H = H; p.T = T; p.scale = softmax_scale;
+    hipLaunchKernelGGL(attn_bwd_dq_alibi_kernel, dim3((max_seqlen + 255) / 256, H, B), dim3(256), LONG_LDS, (hipStream_t)stream, p, slopes,
+                       slopes_batch_stride);
+    hipLaunchKernelGGL(attn_bwd_dkv_alibi_kernel, dim3((max_seqlen + 127) / 128, H, B), dim3(256), LONG_LDS_DKV, (hipStream_t)stream, p,
+                       slopes, slopes_batch_stride);
     return done();
 }
 

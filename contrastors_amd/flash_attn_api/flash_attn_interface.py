@@ -24,7 +24,7 @@ def _draw_philox(device):
 
 class _VarlenQKVPacked(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, cu_seqlens, max_seqlen, scale, dropout_p=0.0, window=None):
+    def forward(ctx, qkv, cu_seqlens, max_seqlen, scale, dropout_p=0.0, window=None, slopes=None):
         if qkv.dtype != torch.bfloat16 or qkv.dim() != 4 or qkv.shape[1] != 3 or qkv.shape[3] not in (32, 64):
             raise NotImplementedError("qkv must be bf16 (T,3,H,D) with head_dim D = 32 or 64")
         d32 = qkv.shape[3] == 32  # the head-pair kernels of csrc/attn_d32.hip
@@ -32,6 +32,8 @@ class _VarlenQKVPacked(torch.autograd.Function):
             raise NotImplementedError("attention dropout > 0 at head_dim 32 is not built")
         if d32 and window is not None:
             raise NotImplementedError("a finite window_size at head_dim 32 is not built")
+        if d32 and slopes is not None:
+            raise NotImplementedError("alibi_slopes at head_dim 32 is not built")
         qkv = qkv.contiguous()
         T, _, H, D = qkv.shape
         B = cu_seqlens.numel() - 1
@@ -39,7 +41,12 @@ class _VarlenQKVPacked(torch.autograd.Function):
         out = torch.empty(T, H, D, dtype=qkv.dtype, device=qkv.device)
         lse = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
         rng = None
-        if d32:
+        if slopes is not None:  # ALiBi: the kernels of csrc/attn_alibi.inc (no dropout, no window: _alibi_of refused them)
+            slopes = _alibi_slopes(slopes, B, H, qkv.device)
+            _C.check(_C.lib().cx_attn_varlen_alibi_fwd(qkv.data_ptr(), cu.data_ptr(), slopes.data_ptr(),
+                                                       H if slopes.dim() == 2 else 0, out.data_ptr(), lse.data_ptr(), B, H, T,
+                                                       int(max_seqlen), scale, _C.cur_stream()), "attn fwd (alibi)")
+        elif d32:
             _C.check(_C.lib().cx_attn_varlen_d32_fwd(qkv.data_ptr(), cu.data_ptr(), out.data_ptr(), lse.data_ptr(), B, H, T,
                                                      int(max_seqlen), scale, _C.cur_stream()), "attn fwd (head_dim 32)")
         elif window is not None:  # a finite window: the banded kernels (no dropout, _window_of refused it)
@@ -56,6 +63,7 @@ class _VarlenQKVPacked(torch.autograd.Function):
                                                  B, H, T, int(max_seqlen), scale, _C.cur_stream()), "attn fwd")
         ctx.save_for_backward(qkv, out, lse, cu)
         ctx.meta = (B, H, T, int(max_seqlen), scale, float(dropout_p), rng, window)
+        ctx.slopes = slopes
         return out
 
     @staticmethod
@@ -65,7 +73,12 @@ class _VarlenQKVPacked(torch.autograd.Function):
         dout = dout.contiguous()
         dqkv = torch.empty_like(qkv)
         delta = torch.empty(H, T, dtype=torch.float32, device=qkv.device)
-        if qkv.shape[3] == 32:
+        if ctx.slopes is not None:
+            sl = ctx.slopes
+            _C.check(_C.lib().cx_attn_varlen_alibi_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                       cu.data_ptr(), sl.data_ptr(), H if sl.dim() == 2 else 0, delta.data_ptr(),
+                                                       dqkv.data_ptr(), B, H, T, mx, scale, _C.cur_stream()), "attn bwd (alibi)")
+        elif qkv.shape[3] == 32:
             _C.check(_C.lib().cx_attn_varlen_d32_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                      cu.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), B, H, T, mx, scale,
                                                      _C.cur_stream()), "attn bwd (head_dim 32)")
@@ -82,7 +95,35 @@ class _VarlenQKVPacked(torch.autograd.Function):
             _C.check(_C.lib().cx_attn_varlen_bwd(dout.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                                  cu.data_ptr(), None, None, delta.data_ptr(), dqkv.data_ptr(), B, H, T, mx,
                                                  scale, _C.cur_stream()), "attn bwd")
-        return dqkv, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None
+
+
+def _alibi_slopes(slopes, B, H, device):
+    """alibi_slopes as the kernels read them: fp32, contiguous, on the qkv device, (H,) or (B, H), finite and >= 0."""
+    slopes = torch.as_tensor(slopes).to(device=device, dtype=torch.float32).contiguous()
+    if tuple(slopes.shape) not in ((H,), (B, H)):
+        raise ValueError(f"alibi_slopes must have shape ({H},) or ({B}, {H}), got {tuple(slopes.shape)}")
+    if not bool((torch.isfinite(slopes) & (slopes >= 0)).all()):
+        raise ValueError("alibi_slopes must be finite and >= 0")
+    return slopes
+
+
+def _alibi_of(alibi_slopes, scale, dropout_p, window):
+    """None without slopes (today's kernels, unchanged); else the slopes, after refusing what the ALiBi kernels do not serve."""
+    if alibi_slopes is None:
+        return None
+    if dropout_p:
+        raise NotImplementedError("alibi_slopes with attention dropout > 0 is not built")
+    if window is not None:
+        raise NotImplementedError("alibi_slopes with a finite window_size is not built")
+    if not scale > 0:
+        raise ValueError("alibi_slopes needs softmax_scale > 0")
+    return alibi_slopes
+
+
+def _no_alibi(alibi_slopes):
+    if alibi_slopes is not None:
+        raise NotImplementedError("alibi_slopes is built for the qkv-packed self-attention forms only")
 
 
 def _window_of(window_size, max_seqlen, dropout_p):
@@ -121,8 +162,9 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
                                      window_size=(-1, -1), alibi_slopes=None, deterministic=False,
                                      return_attn_probs=False):
     _check(dropout_p, causal, return_attn_probs, dropout_ok=True)
-    return _VarlenQKVPacked.apply(qkv, cu_seqlens, max_seqlen, _scale(softmax_scale, qkv.shape[-1]), float(dropout_p),
-                                  _window_of(window_size, max_seqlen, dropout_p))
+    scale, window = _scale(softmax_scale, qkv.shape[-1]), _window_of(window_size, max_seqlen, dropout_p)
+    return _VarlenQKVPacked.apply(qkv, cu_seqlens, max_seqlen, scale, float(dropout_p), window,
+                                  _alibi_of(alibi_slopes, scale, dropout_p, window))
 
 
 def flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1),
@@ -131,8 +173,9 @@ def flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=Fal
     _check(dropout_p, causal, return_attn_probs, dropout_ok=True)
     B, S = qkv.shape[:2]
     cu = torch.arange(0, (B + 1) * S, S, dtype=torch.int32, device=qkv.device)
-    out = _VarlenQKVPacked.apply(qkv.reshape(B * S, *qkv.shape[2:]), cu, S, _scale(softmax_scale, qkv.shape[-1]),
-                                 float(dropout_p), _window_of(window_size, S, dropout_p))
+    scale, window = _scale(softmax_scale, qkv.shape[-1]), _window_of(window_size, S, dropout_p)
+    out = _VarlenQKVPacked.apply(qkv.reshape(B * S, *qkv.shape[2:]), cu, S, scale, float(dropout_p), window,
+                                 _alibi_of(alibi_slopes, scale, dropout_p, window))
     return out.view(B, S, *out.shape[1:])
 
 
@@ -185,6 +228,7 @@ def flash_attn_varlen_kvpacked_func(q, kv, cu_seqlens_q, cu_seqlens_k, max_seqle
     """(Tq,H,64) x (Tk,2,H,64) -> (Tq,H,64): FlashAttentionPooling's varlen branch (sc/layers/attention.py:391-419)."""
     _check(dropout_p, causal, return_attn_probs)
     _no_window(window_size)
+    _no_alibi(alibi_slopes)
     return _VarlenKVPacked.apply(q, kv, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k,
                                  _scale(softmax_scale, q.shape[-1]))
 
@@ -194,6 +238,7 @@ def flash_attn_kvpacked_func(q, kv, dropout_p=0.0, softmax_scale=None, causal=Fa
     """(B,Sq,H,64) x (B,Sk,2,H,64) -> (B,Sq,H,64): FlashAttentionPooling's fixed-length branch (attention.py:420-428)."""
     _check(dropout_p, causal, return_attn_probs)
     _no_window(window_size)
+    _no_alibi(alibi_slopes)
     B, Sq = q.shape[:2]
     Sk = kv.shape[1]
     cu_q = torch.arange(0, (B + 1) * Sq, Sq, dtype=torch.int32, device=q.device)

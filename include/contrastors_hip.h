@@ -342,6 +342,18 @@ int cx_attn_varlen_d32_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, uint1
 int cx_attn_varlen_d32_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
                            const int32_t* cu_seqlens, float* delta, uint16_t* dqkv, int B, int H, int T, int max_seqlen,
                            float softmax_scale, void* stream);
+/* self-attention with ALiBi, flash_attn_*_qkvpacked_func(alibi_slopes = ...) (csrc/attn_alibi.inc), non-causal:
+ * s_ij = softmax_scale * (q_i . k_j) - slope[b, h] * |i - j| for rows i, j of one sequence, out = softmax(s) V, lse =
+ * logsumexp_j s_ij (the bias is inside).  slopes: fp32, (H,) with slopes_batch_stride 0 or (B, H) with slopes_batch_stride
+ * H, finite and >= 0; a slope of 0 gives plain attention for that head.  Layouts as cx_attn_varlen_window_fwd/_bwd, head_dim
+ * 64, any max_seqlen < 2^24, no rotary tables, no dropout.  A null slopes, softmax_scale <= 0 or another stride is
+ * CX_ERR_ARG.  bwd: delta is written by the dQ kernel, dqkv fully overwritten, no atomics (the same bits every run); the
+ * slopes get no gradient.  Additive: cx_abi_version stays as it is. */
+int cx_attn_varlen_alibi_fwd(const uint16_t* qkv, const int32_t* cu_seqlens, const float* slopes, int slopes_batch_stride,
+                             uint16_t* out, float* lse, int B, int H, int T, int max_seqlen, float softmax_scale, void* stream);
+int cx_attn_varlen_alibi_bwd(const uint16_t* dout, const uint16_t* qkv, const uint16_t* out, const float* lse,
+                             const int32_t* cu_seqlens, const float* slopes, int slopes_batch_stride, float* delta,
+                             uint16_t* dqkv, int B, int H, int T, int max_seqlen, float softmax_scale, void* stream);
 /* standalone K11 (apply_rotary_emb_func on a packed qkv, in place on q and k; sign=-1 gives the backward). */
 int cx_rotary_qkv_inplace(uint16_t* qkv, const int32_t* cu_seqlens, const float* rot_cos, const float* rot_sin,
                           int B, int H, int T, int max_seqlen, int sign, void* stream);
