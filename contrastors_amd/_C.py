@@ -180,6 +180,9 @@ _SIGS = {
                                         vp, vp]),
     "cx_xent_fwd": (i32, [vp, i32, vp, vp, vp, i32, i32, i64, f32, i64, vp]),
     "cx_xent_bwd": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, i64, f32, i64, vp]),
+    "cx_linear_xent_ws_floats": (i64, [i32, i32]),
+    "cx_linear_xent_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i64, vp]),
+    "cx_linear_xent_grad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, vp]),
     "cx_grad_sq_norm": (i32, [vp, i64, vp, vp]),
     "cx_adamw_clip_step": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, vp, f32, vp]),
     "cx_ema_update": (i32, [vp, vp, i64, f32, vp]),

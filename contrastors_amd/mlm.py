@@ -6,7 +6,8 @@ One encoder call (`cx_encoder_forward_hidden`) yields the (T, d) hidden states o
 `dense_seq_output` only the rows that carry a label (~15-30 %) go through the head: transform (Linear -> SiLU / GELU ->
 LayerNorm), the vocabulary projection tied to the word-embedding matrix (bf16 MFMA GEMM, 30528-way), and the fused
 cross-entropy kernel with in-place backward (K12) -- the (M, V) logits are written once and overwritten by their own
-gradient.  State-dict keys are the reference's (`bert.*`, `cls.predictions.transform.*`, `cls.predictions.decoder.bias`;
+gradient.  With `logit_free` (the default above 65 536 tokens) projection and loss are one op that never forms the logits
+(contrastors_amd/linear_xent.py, DESIGN.md 7u).  State-dict keys are the reference's (`bert.*`, `cls.predictions.transform.*`, `cls.predictions.decoder.bias`;
 the decoder weight is the embedding matrix and is not stored twice).
 """
 from __future__ import annotations
@@ -21,6 +22,7 @@ from .config import Config
 from .flash_attn_api.losses.cross_entropy import CrossEntropyLoss
 from .flash_attn_api.ops.fused_dense import fused_dense_func
 from .flash_attn_api.ops.layer_norm import layer_norm
+from .linear_xent import linear_cross_entropy
 from .nomic_bert import NomicBertConfig, NomicBertEngine, VarlenBatch
 from .optimizer import FusedAdamW
 
@@ -28,10 +30,13 @@ _WORD = "embeddings.word_embeddings.weight"
 
 
 class NomicBertForPreTraining(torch.nn.Module):
-    def __init__(self, config: NomicBertConfig, device="cuda", seed: Optional[int] = None, dense_seq_output: bool = True):
+    def __init__(self, config: NomicBertConfig, device="cuda", seed: Optional[int] = None, dense_seq_output: bool = True,
+                 logit_free: Optional[bool] = None):
         super().__init__()
         self.config = config
         self.dense_seq_output = dense_seq_output
+        # the loss without the (M, V) logits (contrastors_amd/linear_xent.py); None: on for vocabularies whose logits do not fit
+        self.logit_free = config.vocab_size > 65536 if logit_free is None else bool(logit_free)
         self.bert = NomicBertEngine(config, device=device, pooling="mean", normalize=False, seed=seed)
         d, V = config.n_embd, config.vocab_size
         dev = self.bert.device_
@@ -66,11 +71,13 @@ class NomicBertForPreTraining(torch.nn.Module):
         approx = "tanh" if self.config.activation_function in ("gelu_new", "gelu_fast", "gelu_pytorch_tanh") else "none"
         return torch.nn.functional.gelu(x, approximate=approx)
 
-    def head(self, hidden: torch.Tensor) -> torch.Tensor:
+    def transform(self, hidden: torch.Tensor) -> torch.Tensor:
         h = fused_dense_func(hidden, self.dense_weight, self.dense_bias)
         h = self._act(h)
-        h = layer_norm(h, self.ln_weight, self.ln_bias, self.config.layer_norm_epsilon)
-        return fused_dense_func(h, self._tied_weight(), self.decoder_bias)
+        return layer_norm(h, self.ln_weight, self.ln_bias, self.config.layer_norm_epsilon)
+
+    def head(self, hidden: torch.Tensor) -> torch.Tensor:
+        return fused_dense_func(self.transform(hidden), self._tied_weight(), self.decoder_bias)
 
     def forward(self, input_ids, position_ids=None, token_type_ids=None, attention_mask=None, labels=None):
         """labels: (B, S) int64, -100 on every position that is not a prediction target (padding included)."""
@@ -89,6 +96,9 @@ class NomicBertForPreTraining(torch.nn.Module):
         if self.dense_seq_output:
             idx = torch.nonzero(lab >= 0, as_tuple=False).flatten()  # :650-653 masked_token_idx
             hidden, lab = hidden.index_select(0, idx), lab[idx]
+        if self.logit_free:
+            loss = linear_cross_entropy(self.transform(hidden), self._tied_weight(), self.decoder_bias, lab)
+            return SimpleNamespace(loss=loss, prediction_logits=None)
         logits = self.head(hidden)
         loss = self.mlm_loss(logits, lab).float()
         return SimpleNamespace(loss=loss, prediction_logits=logits)

@@ -1034,6 +1034,24 @@ int cx_xent_fwd(const void* logits, int logits_bf16, const int64_t* labels, floa
 int cx_xent_bwd(const float* dloss, const void* logits, int logits_bf16, const float* lse, const int64_t* labels,
                 void* dlogits, int N, int V, long ld, long ld_d, float logit_scale, long ignore_index, void* stream);
 
+/* ---- logit-free MLM head: the vocabulary projection fused with K12 (csrc/linear_xent.hip).  z = X W^T + bias is
+ *      never written.  X: (M, K) bf16, row stride ldx (% 8); W: (V, K) bf16 row-major; bias: fp32[V] or NULL; labels int64[M]
+ *      (== ignore_index, < 0 or >= V -> loss exactly 0, zero gradient row).  K % 64 == 0, 64 <= K <= 1024, any M >= 1, any V >= 1
+ *      (else CX_ERR_SHAPE); X, W, bias, G, GT 16-byte aligned (CX_ERR_ALIGN).  No atomics: a repeated call gives the same bits.
+ *      fwd: lse[i] = log sum_j exp(z_ij), loss[i] = lse[i] - z[i][label_i], both fp32[M]; ws: cx_linear_xent_ws_floats(M, V) floats.
+ *      grad, for the column chunk [v0, v0 + Vc), v0 % 128 == 0, v0 + Vc <= V: with Vp = round_up(Vc, 128), Mp = round_up(M, 128)
+ *        G:(M, Vp) and GT:(Vp, Mp) bf16 <- bf16((exp(z - lse) - [col == label]) * dloss[row]) and its transpose; ignored rows,
+ *        columns >= v0 + Vc and rows >= M are written as zeros (every element of both buffers is written);
+ *        dbias (fp32[Vc], NULL = skip) <- the column sums of G in a fixed order.
+ *      The caller follows with dX += G W[v0 : v0 + Vc] and dW[v0 : v0 + Vc] = GT X on the bf16 GEMM entries above.
+ *      Additive: cx_abi_version stays 10. */
+long cx_linear_xent_ws_floats(int M, int V);
+int cx_linear_xent_fwd(const uint16_t* X, const uint16_t* W, const float* bias, const int64_t* labels, float* ws, float* lse,
+                       float* loss, int M, int V, int K, int ldx, long ignore_index, void* stream);
+int cx_linear_xent_grad(const uint16_t* X, const uint16_t* W, const float* bias, const int64_t* labels, const float* lse,
+                        const float* dloss, uint16_t* G, uint16_t* GT, float* dbias, int M, int V, int K, int ldx, int v0, int Vc,
+                        long ignore_index, void* stream);
+
 /* ---- fused optimizer tail of training_step (replaces torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW.step as
  *      sc/trainers/base.py:362-385 and sc/optimizer.py:7-47 use them).  fp32, 16-B aligned contiguous buffers.
  *      cx_grad_sq_norm ADDS sum(grad^2) to *sq_norm_accum (device double, zeroed by the caller; call once per gradient
